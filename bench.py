@@ -9,6 +9,10 @@ Driver contract:
 W untimed warmup steps, then EXACTLY K timed steps bracketed by
 barrier + torch.cuda.synchronize on both sides; time is MAX over ranks;
 rank 0 prints ONE JSON line.
+--dump-outputs DIR additionally saves the last timed step's loss and a
+seeded sample of its logits as DIR/<name>.npy; inputs and weights are
+seeded, so two builds can be compared output for output.  --full is where
+secondary measurements belong; there are none today.
 """
 import argparse
 import json
@@ -43,7 +47,49 @@ def parse_args():
                    help="selective act-ckpt: every k-th layer skips "
                         "recompute (0 = checkpoint all layers, -1 = auto "
                         "from free HBM after optimizer init)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed "
+                        "step's forward returned (loss, logits) to "
+                        "DIR/<name>.npy as float32; large arrays are "
+                        "reduced to a fixed seeded sample")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement; this "
+                        "benchmark has none beyond the headline figure, so "
+                        "a full run does the same work as a plain one")
     return p.parse_args()
+
+
+# at most this many elements of each dumped array (4 MiB as float32)
+_DUMP_MAX_ELEMS = 1 << 20
+
+
+def sample_outputs(out) -> dict:
+    """Tensors a caller of the model's forward receives, flattened to
+    float32.  An array above _DUMP_MAX_ELEMS is reduced to the elements at
+    a fixed seeded set of flat indices, so two builds sample the same
+    positions."""
+    kept = {}
+    for name in ("loss", "logits", "prediction_logits",
+                 "seq_relationship_logits"):
+        t = getattr(out, name, None)
+        if not torch.is_tensor(t):
+            continue
+        flat = t.detach().reshape(-1)
+        if flat.numel() > _DUMP_MAX_ELEMS:
+            g = torch.Generator(device="cpu").manual_seed(2024)
+            idx = torch.randint(0, flat.numel(), (_DUMP_MAX_ELEMS,),
+                                generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        kept[name] = flat.float()
+    return kept
+
+
+def write_outputs(out_dir: str, kept: dict) -> None:
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in kept.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"),
+                t.cpu().numpy().astype(np.float32, copy=False))
 
 
 _REPO = os.path.dirname(os.path.abspath(__file__))
@@ -305,11 +351,16 @@ def main():
             batches.append(dict(input_ids=ids, labels=ids))
 
     step_idx = [0]
+    dumped = {}
 
-    def step():
+    def step(keep=False):
         batch = batches[step_idx[0] % len(batches)]
         step_idx[0] += 1
         out = model(**batch)
+        if keep:
+            # sampled before backward frees the logits; stays on the device
+            # so the timed region gains no host synchronisation
+            dumped.update(sample_outputs(out))
         opt.zero_grad()
         out.loss.backward()
         opt.step()
@@ -344,8 +395,9 @@ def main():
     if torch.cuda.is_available():
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(keep=args.dump_outputs is not None
+                    and i == args.steps - 1)
     if torch.cuda.is_available():
         torch.cuda.synchronize()
     if world > 1:
@@ -374,6 +426,9 @@ def main():
     mfu = tflops_per_gpu / 2500.0  # MI355X dense bf16 peak ~2.5 PF/s
     if is_sd:  # token-based MFU formula does not apply to the conv UNet
         tflops_per_gpu, mfu = None, None
+
+    if rank == 0 and args.dump_outputs is not None:
+        write_outputs(args.dump_outputs, dumped)
 
     if rank == 0:
         print(json.dumps({
