@@ -68,8 +68,9 @@ class ClipFinetune(FengshenModule):
             dist.all_gather(gt, txt)
             img, txt = torch.cat(gi), torch.cat(gt)
         sim = img.float() @ txt.float().t()
-        r1_i2t = (sim.argmax(dim=1) == torch.arange(len(sim))).float().mean()
-        r1_t2i = (sim.argmax(dim=0) == torch.arange(len(sim))).float().mean()
+        idx = torch.arange(len(sim), device=sim.device)
+        r1_i2t = (sim.argmax(dim=1) == idx).float().mean()
+        r1_t2i = (sim.argmax(dim=0) == idx).float().mean()
         self.log("val_r1_i2t", r1_i2t)
         self.log("val_r1_t2i", r1_t2i)
         self._val_img.clear()

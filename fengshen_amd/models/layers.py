@@ -196,6 +196,30 @@ class ParallelAttention(nn.Module):
         hn = self.head_dim
 
         qkv = self.qkv_proj(x)  # [b, sq, 3h/tp]
+
+        # packed path: rotary in place + strided flash kernels on the
+        # projection output itself — no chunk/transpose/contiguous copies
+        if cache is None and F_ops.use_hip(qkv):
+            from fengshen_amd.ops.flash import (
+                mask_to_klens, packed_attn_eligible, packed_self_attention)
+            drop = self.attention_dropout if self.training else 0.0
+            if packed_attn_eligible(qkv, hn, self.causal, attention_mask,
+                                    drop):
+                klens = None
+                if attention_mask is not None:
+                    klens = mask_to_klens(attention_mask, sq)
+                if attention_mask is None or klens is not None:
+                    cos = sin = None
+                    if self.rotary:
+                        cos, sin = self._rope_tables(qkv.device, sq)
+                    ctx = packed_self_attention(
+                        qkv, np_, cos, sin, 0, self.norm_factor,
+                        causal=self.causal, klens=klens)
+                    out = self.out_proj(ctx)
+                    if isinstance(out, tuple) and self.reduce_output:
+                        out = out[0]
+                    return out
+
         q, k, v = qkv.chunk(3, dim=-1)
         # [b, s, np, hn] -> [b, np, s, hn]
         q = q.view(b, sq, np_, hn).transpose(1, 2)

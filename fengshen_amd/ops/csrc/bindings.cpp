@@ -74,6 +74,18 @@ void fs_flash_attn_bwd_v3(const void*, const void*, const void*, const void*,
                           const void*, const float*, void*, void*, void*,
                           float*, const int*, int, int, int, int, int, float,
                           float, unsigned long long, hipStream_t);
+void fs_flash_attn_fwd_v3_strided(const void*, const void*, const void*,
+                                  void*, float*, const int*, const long*,
+                                  const long*, int, int, int, int, int, float,
+                                  float, unsigned long long, hipStream_t);
+void fs_flash_attn_bwd_v3_strided(const void*, const void*, const void*,
+                                  const void*, const void*, const float*,
+                                  void*, void*, void*, float*, const int*,
+                                  const long*, const long*, const long*,
+                                  const long*, int, int, int, int, int, float,
+                                  float, unsigned long long, hipStream_t);
+void fs_rope_inplace(void*, void*, const float*, const float*, int, int, int,
+                     int, long, long, long, int, int, int, hipStream_t);
 }
 
 // ---------------------------------------------------------------------------
@@ -349,6 +361,142 @@ static std::vector<at::Tensor> flash_attn_bwd(
   return {dq, dk, dv};
 }
 
+// --- strided v3 flash / in-place rotary -----------------------------------
+// Operands are logical [b, h, s, d] bf16 views with arbitrary batch / head /
+// row strides (e.g. thirds of a packed [b, s, 3*h*d] projection output).
+// The kernels use 16-byte vector accesses, so the last dim must be
+// unit-stride and every other stride and the base address 16-byte aligned.
+// All of this is checked here, on the host, before anything is launched.
+static void check_strided_view(const at::Tensor& t, const char* name, int b,
+                               int h, int s, int d) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16, name,
+              ": must be a bf16 GPU tensor");
+  TORCH_CHECK(t.dim() == 4 && t.size(0) == b && t.size(1) == h &&
+                  t.size(2) == s && t.size(3) == d,
+              name, ": expected shape [", b, ", ", h, ", ", s, ", ", d, "]");
+  TORCH_CHECK(t.stride(3) == 1, name, ": last dim must be unit-stride");
+  for (int i = 0; i < 3; ++i)
+    TORCH_CHECK(t.stride(i) > 0 && t.stride(i) % 8 == 0, name, ": stride ", i,
+                " (", t.stride(i), ") must be a positive multiple of 8");
+  TORCH_CHECK(t.storage_offset() % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              name, ": base offset must be a multiple of 8 elements");
+  // the view must stay inside its storage
+  const int64_t last = t.storage_offset() + (b - 1) * t.stride(0) +
+                       (h - 1) * t.stride(1) + (s - 1) * t.stride(2) + d;
+  TORCH_CHECK(last * 2 <= (int64_t)t.storage().nbytes(), name,
+              ": view runs past its storage");
+}
+
+static void check_same_strides(const at::Tensor& a, const at::Tensor& b,
+                               const char* what) {
+  TORCH_CHECK(a.strides() == b.strides(), what, " must share strides");
+}
+
+static void strides3(const at::Tensor& t, long out[3]) {
+  out[0] = t.stride(0);
+  out[1] = t.stride(1);
+  out[2] = t.stride(2);
+}
+
+static const int* checked_klens(const c10::optional<at::Tensor>& klens,
+                                bool causal, int b) {
+  if (!klens.has_value()) return nullptr;
+  TORCH_CHECK(!causal, "flash v3: klens only with causal=False");
+  TORCH_CHECK(klens->is_cuda() && klens->scalar_type() == at::kInt &&
+              klens->numel() == b && klens->is_contiguous());
+  return klens->data_ptr<int>();
+}
+
+// Writes o in place; returns lse [b, h, s] fp32.
+static at::Tensor flash_attn_fwd_v3_strided(
+    at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, double scale,
+    bool causal, c10::optional<at::Tensor> klens) {
+  TORCH_CHECK(q.dim() == 4, "q must be [b, h, s, d]");
+  const int b = q.size(0), h = q.size(1), s = q.size(2), d = q.size(3);
+  TORCH_CHECK((d == 128 || d == 96 || d == 64) && s % 64 == 0 && s >= 64,
+              "flash v3: d in {64, 96, 128}, s a multiple of 64");
+  check_strided_view(q, "q", b, h, s, d);
+  check_strided_view(k, "k", b, h, s, d);
+  check_strided_view(v, "v", b, h, s, d);
+  check_strided_view(o, "o", b, h, s, d);
+  check_same_strides(q, k, "q and k");
+  check_same_strides(q, v, "q and v");
+  const int* klp = checked_klens(klens, causal, b);
+  long qs[3], os[3];
+  strides3(q, qs);
+  strides3(o, os);
+  auto lse = at::empty({b, h, s}, q.options().dtype(at::kFloat));
+  fs_flash_attn_fwd_v3_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                               o.data_ptr(), lse.data_ptr<float>(), klp, qs,
+                               os, b, h, s, d, causal ? 1 : 0, (float)scale,
+                               0.f, 0ull, cur_stream());
+  return lse;
+}
+
+// Writes dq, dk, dv in place.
+static void flash_attn_bwd_v3_strided(
+    at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor dout,
+    at::Tensor lse, at::Tensor dq, at::Tensor dk, at::Tensor dv, double scale,
+    bool causal, c10::optional<at::Tensor> klens) {
+  TORCH_CHECK(q.dim() == 4, "q must be [b, h, s, d]");
+  const int b = q.size(0), h = q.size(1), s = q.size(2), d = q.size(3);
+  TORCH_CHECK((d == 128 || d == 96 || d == 64) && s % 64 == 0 && s >= 64,
+              "flash v3: d in {64, 96, 128}, s a multiple of 64");
+  check_strided_view(q, "q", b, h, s, d);
+  check_strided_view(k, "k", b, h, s, d);
+  check_strided_view(v, "v", b, h, s, d);
+  check_strided_view(o, "o", b, h, s, d);
+  check_strided_view(dout, "dout", b, h, s, d);
+  check_strided_view(dq, "dq", b, h, s, d);
+  check_strided_view(dk, "dk", b, h, s, d);
+  check_strided_view(dv, "dv", b, h, s, d);
+  check_same_strides(q, k, "q and k");
+  check_same_strides(q, v, "q and v");
+  check_same_strides(dq, dk, "dq and dk");
+  check_same_strides(dq, dv, "dq and dv");
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat &&
+              lse.is_contiguous() && lse.numel() == (int64_t)b * h * s,
+              "lse must be contiguous fp32 [b, h, s]");
+  const int* klp = checked_klens(klens, causal, b);
+  long qs[3], os[3], dos[3], gs[3];
+  strides3(q, qs);
+  strides3(o, os);
+  strides3(dout, dos);
+  strides3(dq, gs);
+  auto delta = at::empty({b, h, s}, q.options().dtype(at::kFloat));
+  fs_flash_attn_bwd_v3_strided(
+      q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(),
+      lse.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+      delta.data_ptr<float>(), klp, qs, os, dos, gs, b, h, s, d,
+      causal ? 1 : 0, (float)scale, 0.f, 0ull, cur_stream());
+}
+
+// Rotates q and k ([b, np, s, hn] views sharing strides) in place;
+// bwd = transpose rotation for gradients.  cos/sin: [S, hn] fp32.
+static void rope_inplace(at::Tensor q, at::Tensor k, at::Tensor cos,
+                         at::Tensor sin, int64_t offset, bool bwd) {
+  TORCH_CHECK(q.dim() == 4, "q must be [b, np, s, hn]");
+  const int b = q.size(0), np = q.size(1), s = q.size(2), hn = q.size(3);
+  TORCH_CHECK((hn / 2) % 8 == 0 && hn % 2 == 0,
+              "head_dim/2 must be divisible by 8");
+  check_strided_view(q, "q", b, np, s, hn);
+  check_strided_view(k, "k", b, np, s, hn);
+  check_same_strides(q, k, "q and k");
+  TORCH_CHECK(cos.is_cuda() && sin.is_cuda() &&
+              cos.scalar_type() == at::kFloat &&
+              sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
+              sin.is_contiguous() && cos.dim() == 2 && cos.size(1) == hn &&
+              sin.sizes() == cos.sizes(),
+              "cos/sin must be contiguous fp32 [S, hn]");
+  TORCH_CHECK(offset >= 0 && offset + s <= cos.size(0),
+              "rope table too short for offset + s");
+  fs_rope_inplace(q.data_ptr(), k.data_ptr(), cos.data_ptr<float>(),
+                  sin.data_ptr<float>(), b, np, s, hn, q.stride(0),
+                  q.stride(1), q.stride(2), (int)offset, bwd ? 1 : 0,
+                  fs_dtype(q), cur_stream());
+}
+
 // x [b, in] bf16, q8 [out, in] int8, scale [out] fp32 -> y [b, out] bf16
 static at::Tensor w8_gemv(at::Tensor q8, at::Tensor scale, at::Tensor x) {
   TORCH_CHECK(q8.scalar_type() == at::kChar && x.scalar_type() == at::kBFloat16);
@@ -497,6 +645,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
     return std::vector<at::Tensor>{o, lse};
   });
   mod.def("flash_attn_bwd", &flash_attn_bwd);
+  mod.def("flash_attn_fwd_v3_strided", &flash_attn_fwd_v3_strided);
+  mod.def("flash_attn_bwd_v3_strided", &flash_attn_bwd_v3_strided);
+  mod.def("rope_inplace", &rope_inplace);
   mod.def("rms_norm_fwd", &rms_norm_fwd);
   mod.def("rms_norm_bwd", &rms_norm_bwd);
   mod.def("layer_norm_fwd", &layer_norm_fwd);

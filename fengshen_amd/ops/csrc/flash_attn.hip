@@ -993,6 +993,45 @@ extern "C" void fs_flash_attn_bwd(const void* q, const void* k, const void* v,
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
+// Element strides of a logical [b, h, s, D] tensor whose last dim is
+// unit-stride.  The v3 kernels address every operand through one of these,
+// so they read q/k/v straight out of a packed [b, s, 3*h*D] projection
+// output and write O / dQ / dK / dV where the next GEMM wants them.
+// Every stride (and base offset) must be a multiple of 8 elements: all
+// global accesses are 16-byte vectors.
+struct FaStrides {
+  long b, h, r;
+};
+
+// delta[b,h,s] = rowsum(dO * O) over strided rows; same per-row arithmetic
+// as flash_delta_kernel.  Grid (x, h, b): blockIdx.y/z pick the head and
+// batch, so the [b, h, s] output index needs no division; the 4 waves of a
+// block walk the s rows of that head in a grid-stride loop over x.
+template <int D>
+__global__ __launch_bounds__(256)
+void flash_delta_v3_kernel(const bf16_t* __restrict__ dO,
+                           const bf16_t* __restrict__ O,
+                           float* __restrict__ delta, FaStrides dos,
+                           FaStrides os, int h, int s) {
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const bf16_t* dob = dO + blockIdx.z * dos.b + blockIdx.y * dos.h;
+  const bf16_t* ob = O + blockIdx.z * os.b + blockIdx.y * os.h;
+  float* dl = delta + ((long)blockIdx.z * h + blockIdx.y) * s;
+  for (int row = blockIdx.x * 4 + wid; row < s; row += gridDim.x * 4) {
+    const bf16_t* dop = dob + row * dos.r;
+    const bf16_t* op = ob + row * os.r;
+    float sacc = 0.f;
+    for (int i = lane * 2; i < D; i += 128) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        sacc += __bfloat162float(dop[i + j]) * __bfloat162float(op[i + j]);
+    }
+    sacc = wave_reduce_sum(sacc);
+    if (lane == 0) dl[row] = sacc;
+  }
+}
+
 template <int D, bool CAUSAL, bool HAS_DROP>
 __global__ __launch_bounds__(FA_WAVES * 64)
 void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
@@ -1001,6 +1040,7 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
                               bf16_t* __restrict__ O,
                               float* __restrict__ LSE,
                               const int* __restrict__ klens,
+                              FaStrides qs, FaStrides os,
                               int b, int h, int s, float scale,
                               unsigned int drop_thresh, float keep_scale,
                               unsigned long long drop_seed) {
@@ -1021,10 +1061,11 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
   const int hi = lane >> 5;      // lane half
   const int ln = lane & 31;
   const long bh = (long)blockIdx.z * h + blockIdx.y;
-  const bf16_t* Qp = Q + bh * s * D;
-  const bf16_t* Kp = K + bh * s * D;
-  const bf16_t* Vp = V + bh * s * D;
-  bf16_t* Op = O + bh * s * D;
+  const long qoff = blockIdx.z * qs.b + blockIdx.y * qs.h;
+  const bf16_t* Qp = Q + qoff;
+  const bf16_t* Kp = K + qoff;
+  const bf16_t* Vp = V + qoff;
+  bf16_t* Op = O + blockIdx.z * os.b + blockIdx.y * os.h;
 
   const int klen = CAUSAL ? s : min(klens ? klens[blockIdx.z] : s, s);
 
@@ -1038,7 +1079,7 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     bf16x8 raw = *reinterpret_cast<const bf16x8*>(
-        Qp + (long)my_q * D + c * 16 + hi * 8);
+        Qp + (long)my_q * qs.r + c * 16 + hi * 8);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       unsigned short u = (unsigned short)raw[j];
@@ -1076,8 +1117,8 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
     if (i < ELEMS) {
       const long kr = min(i / D, s - 1);
       const int kc = i % D;
-      k_reg[sweep] = *reinterpret_cast<const bf16x8*>(Kp + kr * D + kc);
-      v_reg[sweep] = *reinterpret_cast<const bf16x8*>(Vp + kr * D + kc);
+      k_reg[sweep] = *reinterpret_cast<const bf16x8*>(Kp + kr * qs.r + kc);
+      v_reg[sweep] = *reinterpret_cast<const bf16x8*>(Vp + kr * qs.r + kc);
     }
   }
 
@@ -1110,8 +1151,8 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
         if (i < ELEMS) {
           const long kr = min((long)(nb + i / D), (long)s - 1);
           const int kc = i % D;
-          k_reg[sweep] = *reinterpret_cast<const bf16x8*>(Kp + kr * D + kc);
-          v_reg[sweep] = *reinterpret_cast<const bf16x8*>(Vp + kr * D + kc);
+          k_reg[sweep] = *reinterpret_cast<const bf16x8*>(Kp + kr * qs.r + kc);
+          v_reg[sweep] = *reinterpret_cast<const bf16x8*>(Vp + kr * qs.r + kc);
         }
       }
     }
@@ -1272,7 +1313,7 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
         __shfl(my_inv_l, (r & 3) + 8 * (r >> 2) + 4 * hi, 64);
 #pragma unroll
     for (int t = 0; t < NTO; ++t) {
-      Op[(long)qrow * D + t * 32 + ln] =
+      Op[(long)qrow * os.r + t * 32 + ln] =
           __float2bfloat16(o_acc[t][r] * inv_l);
     }
   }
@@ -1281,12 +1322,14 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
   }
 }
 
-extern "C" void fs_flash_attn_fwd_v3(const void* q, const void* k,
-                                     const void* v, void* o, float* lse,
-                                     const int* klens, int b, int h, int s,
-                                     int d, int causal, float scale,
-                                     float drop_p, unsigned long long seed,
-                                     hipStream_t stream) {
+// qs3 / os3: (batch, head, row) element strides of q|k|v and of o.
+extern "C" void fs_flash_attn_fwd_v3_strided(
+    const void* q, const void* k, const void* v, void* o, float* lse,
+    const int* klens, const long* qs3, const long* os3, int b, int h, int s,
+    int d, int causal, float scale, float drop_p, unsigned long long seed,
+    hipStream_t stream) {
+  const FaStrides qs{qs3[0], qs3[1], qs3[2]};
+  const FaStrides os{os3[0], os3[1], os3[2]};
   dim3 grid((s + V3_QBLK - 1) / V3_QBLK, h, b);
   dim3 block(FA_WAVES * 64);
   const unsigned int dth =
@@ -1295,7 +1338,8 @@ extern "C" void fs_flash_attn_fwd_v3(const void* q, const void* k,
 #define V3F(DD, CC, DR) hipLaunchKernelGGL( \
     (flash_attn_fwd_v3_kernel<DD, CC, DR>), \
     grid, block, 0, stream, (const bf16_t*)q, (const bf16_t*)k, \
-    (const bf16_t*)v, (bf16_t*)o, lse, klens, b, h, s, scale, dth, ksc, seed)
+    (const bf16_t*)v, (bf16_t*)o, lse, klens, qs, os, b, h, s, scale, dth, \
+    ksc, seed)
   if (dth) {
     if (d == 128 && causal) V3F(128, true, true);
     else if (d == 128) V3F(128, false, true);
@@ -1312,6 +1356,17 @@ extern "C" void fs_flash_attn_fwd_v3(const void* q, const void* k,
     else V3F(64, false, false);
   }
 #undef V3F
+}
+
+extern "C" void fs_flash_attn_fwd_v3(const void* q, const void* k,
+                                     const void* v, void* o, float* lse,
+                                     const int* klens, int b, int h, int s,
+                                     int d, int causal, float scale,
+                                     float drop_p, unsigned long long seed,
+                                     hipStream_t stream) {
+  const long c3[3] = {(long)h * s * d, (long)s * d, (long)d};
+  fs_flash_attn_fwd_v3_strided(q, k, v, o, lse, klens, c3, c3, b, h, s, d,
+                               causal, scale, drop_p, seed, stream);
 }
 
 // ===========================================================================
@@ -1335,6 +1390,7 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
                                  const float* __restrict__ Delta,
                                  bf16_t* __restrict__ dQ,
                                  const int* __restrict__ klens,
+                                 FaStrides qs, FaStrides dos, FaStrides gs,
                                  int b, int h, int s, float scale,
                                  unsigned int drop_thresh, float keep_scale,
                                  unsigned long long drop_seed) {
@@ -1352,11 +1408,12 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
   const int hi = lane >> 5;
   const int ln = lane & 31;
   const long bh = (long)blockIdx.z * h + blockIdx.y;
-  const bf16_t* Qp = Q + bh * s * D;
-  const bf16_t* Kp = K + bh * s * D;
-  const bf16_t* Vp = V + bh * s * D;
-  const bf16_t* dOp = dO + bh * s * D;
-  bf16_t* dQp = dQ + bh * s * D;
+  const long qoff = blockIdx.z * qs.b + blockIdx.y * qs.h;
+  const bf16_t* Qp = Q + qoff;
+  const bf16_t* Kp = K + qoff;
+  const bf16_t* Vp = V + qoff;
+  const bf16_t* dOp = dO + blockIdx.z * dos.b + blockIdx.y * dos.h;
+  bf16_t* dQp = dQ + blockIdx.z * gs.b + blockIdx.y * gs.h;
   const float* lse = LSE + bh * s;
   const float* dlt = Delta + bh * s;
 
@@ -1371,7 +1428,7 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     bf16x8 raw = *reinterpret_cast<const bf16x8*>(
-        Qp + (long)my_q * D + c * 16 + hi * 8);
+        Qp + (long)my_q * qs.r + c * 16 + hi * 8);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       unsigned short u = (unsigned short)raw[j];
@@ -1380,7 +1437,7 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
     }
     q_frag[c] = raw;
     do_frag[c] = *reinterpret_cast<const bf16x8*>(
-        dOp + (long)my_q * D + c * 16 + hi * 8);
+        dOp + (long)my_q * dos.r + c * 16 + hi * 8);
   }
   const float lse_r = lse[my_q];
   const float dlt_r = dlt[my_q];
@@ -1409,9 +1466,9 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
         const int kr = i / D;
         const int kc = i % D;
         const long krg = min(k_base + kr, s - 1);
-        bf16x8 kk = *reinterpret_cast<const bf16x8*>(Kp + krg * D + kc);
+        bf16x8 kk = *reinterpret_cast<const bf16x8*>(Kp + krg * qs.r + kc);
         *reinterpret_cast<bf16x8*>(k_raw + kr * SWB + kswz(kr, kc * 2)) = kk;
-        bf16x8 vv = *reinterpret_cast<const bf16x8*>(Vp + krg * D + kc);
+        bf16x8 vv = *reinterpret_cast<const bf16x8*>(Vp + krg * qs.r + kc);
         *reinterpret_cast<bf16x8*>(v_raw + kr * SWB + kswz(kr, kc * 2)) = vv;
 #pragma unroll
         for (int j = 0; j < 8; ++j)
@@ -1491,7 +1548,7 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
     const int qrow = q0w + (r & 3) + 8 * (r >> 2) + 4 * hi;
 #pragma unroll
     for (int t = 0; t < NTO; ++t)
-      dQp[(long)qrow * D + t * 32 + ln] = __float2bfloat16(dq_acc[t][r]);
+      dQp[(long)qrow * gs.r + t * 32 + ln] = __float2bfloat16(dq_acc[t][r]);
   }
 }
 
@@ -1511,6 +1568,7 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
                                   bf16_t* __restrict__ dK,
                                   bf16_t* __restrict__ dV,
                                   const int* __restrict__ klens,
+                                  FaStrides qs, FaStrides dos, FaStrides gs,
                                   int b, int h, int s, float scale,
                                   unsigned int drop_thresh, float keep_scale,
                                   unsigned long long drop_seed) {
@@ -1530,12 +1588,14 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
   const int hi = lane >> 5;
   const int ln = lane & 31;
   const long bh = (long)blockIdx.z * h + blockIdx.y;
-  const bf16_t* Qp = Q + bh * s * D;
-  const bf16_t* Kp = K + bh * s * D;
-  const bf16_t* Vp = V + bh * s * D;
-  const bf16_t* dOp = dO + bh * s * D;
-  bf16_t* dKp = dK + bh * s * D;
-  bf16_t* dVp = dV + bh * s * D;
+  const long qoff = blockIdx.z * qs.b + blockIdx.y * qs.h;
+  const bf16_t* Qp = Q + qoff;
+  const bf16_t* Kp = K + qoff;
+  const bf16_t* Vp = V + qoff;
+  const bf16_t* dOp = dO + blockIdx.z * dos.b + blockIdx.y * dos.h;
+  const long goff = blockIdx.z * gs.b + blockIdx.y * gs.h;
+  bf16_t* dKp = dK + goff;
+  bf16_t* dVp = dV + goff;
   const float* lse = LSE + bh * s;
   const float* dlt = Delta + bh * s;
 
@@ -1569,10 +1629,10 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
         const int qr = i / D;
         const int qc = i % D;
         bf16x8 qq = *reinterpret_cast<const bf16x8*>(
-            Qp + (long)(q_base + qr) * D + qc);
+            Qp + (long)(q_base + qr) * qs.r + qc);
         *reinterpret_cast<bf16x8*>(q_raw + qr * SWB + kswz(qr, qc * 2)) = qq;
         bf16x8 dd = *reinterpret_cast<const bf16x8*>(
-            dOp + (long)(q_base + qr) * D + qc);
+            dOp + (long)(q_base + qr) * dos.r + qc);
         *reinterpret_cast<bf16x8*>(do_raw + qr * SWB + kswz(qr, qc * 2)) =
             dd;
 #pragma unroll
@@ -1591,7 +1651,7 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       bf16x8 ka = *reinterpret_cast<const bf16x8*>(
-          Kp + (long)my_kv * D + c * 16 + hi * 8);
+          Kp + (long)my_kv * qs.r + c * 16 + hi * 8);
       bf16x8 qb = *reinterpret_cast<const bf16x8*>(
           q_raw + ln * SWB + kswz(ln, (c * 16 + hi * 8) * 2));
       st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qb, st, 0, 0, 0);
@@ -1603,7 +1663,7 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       bf16x8 va = *reinterpret_cast<const bf16x8*>(
-          Vp + (long)my_kv * D + c * 16 + hi * 8);
+          Vp + (long)my_kv * qs.r + c * 16 + hi * 8);
       bf16x8 db = *reinterpret_cast<const bf16x8*>(
           do_raw + ln * SWB + kswz(ln, (c * 16 + hi * 8) * 2));
       dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, db, dpt, 0, 0, 0);
@@ -1671,8 +1731,8 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
     const int kvrow = kv0w + (r & 3) + 8 * (r >> 2) + 4 * hi;
 #pragma unroll
     for (int t = 0; t < NTO; ++t) {
-      dKp[(long)kvrow * D + t * 32 + ln] = __float2bfloat16(dk_acc[t][r]);
-      dVp[(long)kvrow * D + t * 32 + ln] = __float2bfloat16(dv_acc[t][r]);
+      dKp[(long)kvrow * gs.r + t * 32 + ln] = __float2bfloat16(dk_acc[t][r]);
+      dVp[(long)kvrow * gs.r + t * 32 + ln] = __float2bfloat16(dv_acc[t][r]);
     }
   }
 }
@@ -1681,46 +1741,51 @@ template <int D, bool CAUSAL, bool HAS_DROP>
 static void launch_bwd_v3(const void* q, const void* k, const void* v,
                           const void* o, const void* dout, const float* lse,
                           void* dq, void* dk, void* dv, float* delta_ws,
-                          const int* klens, int b, int h, int s, float scale,
-                          unsigned int dth, float ksc,
+                          const int* klens, FaStrides qs, FaStrides os,
+                          FaStrides dos, FaStrides gs, int b, int h, int s,
+                          float scale, unsigned int dth, float ksc,
                           unsigned long long seed, hipStream_t stream) {
-  const long rows = (long)b * h * s;
   {
-    long blocks = (rows + 3) / 4;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((flash_delta_kernel<D>), dim3((unsigned)blocks),
-                       dim3(256), 0, stream, (const bf16_t*)dout,
-                       (const bf16_t*)o, delta_ws, rows);
+    // at most 16 x-blocks per (batch, head): plenty of blocks to fill the
+    // chip while each wave still streams several rows
+    int bx = (s + 31) / 32;
+    if (bx > 16) bx = 16;
+    hipLaunchKernelGGL((flash_delta_v3_kernel<D>), dim3(bx, h, b), dim3(256),
+                       0, stream, (const bf16_t*)dout, (const bf16_t*)o,
+                       delta_ws, dos, os, h, s);
   }
   dim3 grid((s + V3_QBLK - 1) / V3_QBLK, h, b);
   dim3 block(FA_WAVES * 64);
   hipLaunchKernelGGL((flash_attn_bwd_dq_v3_kernel<D, CAUSAL, HAS_DROP>),
                      grid, block, 0, stream, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout,
-                     lse, delta_ws, (bf16_t*)dq, klens, b, h, s, scale, dth,
-                     ksc, seed);
+                     lse, delta_ws, (bf16_t*)dq, klens, qs, dos, gs, b, h, s,
+                     scale, dth, ksc, seed);
   hipLaunchKernelGGL((flash_attn_bwd_dkv_v3_kernel<D, CAUSAL, HAS_DROP>),
                      grid, block, 0, stream, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout,
-                     lse, delta_ws, (bf16_t*)dk, (bf16_t*)dv, klens, b, h, s,
-                     scale, dth, ksc, seed);
+                     lse, delta_ws, (bf16_t*)dk, (bf16_t*)dv, klens, qs, dos,
+                     gs, b, h, s, scale, dth, ksc, seed);
 }
 
-extern "C" void fs_flash_attn_bwd_v3(const void* q, const void* k,
-                                     const void* v, const void* o,
-                                     const void* dout, const float* lse,
-                                     void* dq, void* dk, void* dv,
-                                     float* delta_ws, const int* klens,
-                                     int b, int h, int s, int d, int causal,
-                                     float scale, float drop_p,
-                                     unsigned long long seed,
-                                     hipStream_t stream) {
+// qs3: q|k|v, os3: o, dos3: dout, gs3: dq|dk|dv (batch, head, row) strides.
+extern "C" void fs_flash_attn_bwd_v3_strided(
+    const void* q, const void* k, const void* v, const void* o,
+    const void* dout, const float* lse, void* dq, void* dk, void* dv,
+    float* delta_ws, const int* klens, const long* qs3, const long* os3,
+    const long* dos3, const long* gs3, int b, int h, int s, int d,
+    int causal, float scale, float drop_p, unsigned long long seed,
+    hipStream_t stream) {
+  const FaStrides qs{qs3[0], qs3[1], qs3[2]};
+  const FaStrides os{os3[0], os3[1], os3[2]};
+  const FaStrides dos{dos3[0], dos3[1], dos3[2]};
+  const FaStrides gs{gs3[0], gs3[1], gs3[2]};
   const unsigned int dth =
       (drop_p > 0.f) ? (unsigned int)(drop_p * 4294967296.0) : 0u;
   const float ksc = (drop_p > 0.f) ? 1.f / (1.f - drop_p) : 1.f;
 #define BWD3(DD, CC, DR) launch_bwd_v3<DD, CC, DR>( \
-      q, k, v, o, dout, lse, dq, dk, dv, delta_ws, klens, b, h, s, scale, \
-      dth, ksc, seed, stream)
+      q, k, v, o, dout, lse, dq, dk, dv, delta_ws, klens, qs, os, dos, gs, \
+      b, h, s, scale, dth, ksc, seed, stream)
   if (dth) {
     if (d == 128 && causal) BWD3(128, true, true);
     else if (d == 128) BWD3(128, false, true);
@@ -1737,4 +1802,19 @@ extern "C" void fs_flash_attn_bwd_v3(const void* q, const void* k,
     else BWD3(64, false, false);
   }
 #undef BWD3
+}
+
+extern "C" void fs_flash_attn_bwd_v3(const void* q, const void* k,
+                                     const void* v, const void* o,
+                                     const void* dout, const float* lse,
+                                     void* dq, void* dk, void* dv,
+                                     float* delta_ws, const int* klens,
+                                     int b, int h, int s, int d, int causal,
+                                     float scale, float drop_p,
+                                     unsigned long long seed,
+                                     hipStream_t stream) {
+  const long c3[3] = {(long)h * s * d, (long)s * d, (long)d};
+  fs_flash_attn_bwd_v3_strided(q, k, v, o, dout, lse, dq, dk, dv, delta_ws,
+                               klens, c3, c3, c3, c3, b, h, s, d, causal,
+                               scale, drop_p, seed, stream);
 }

@@ -385,6 +385,52 @@ __global__ void rope_kernel(const T* __restrict__ x, T* __restrict__ out,
   }
 }
 
+// In-place variant on strided [b, np, s, hn] views (unit last stride): rotates
+// xq and xk, which share the (batch, head, row) element strides sb/sh/sr, so
+// the q and k thirds of a packed [b, s, 3*np*hn] projection output are
+// rotated where they lie.  Each thread reads both halves of its pairs
+// before it writes either, and no pair is shared between threads.  Pairs
+// are walked in (tensor, b, s, head, d) order — memory order of the packed
+// layout.  Same fp32 math and rounding as rope_kernel.
+template <typename T, bool BWD>
+__global__ void rope_inplace_kernel(T* __restrict__ xq, T* __restrict__ xk,
+                                    const float* __restrict__ cos_t,
+                                    const float* __restrict__ sin_t,
+                                    long pairs_per_tensor, int np, int s,
+                                    int h2, int offset, long sb, long sh,
+                                    long sr) {
+  const long stride = (long)gridDim.x * blockDim.x * 8;
+  for (long i0 = (long)(blockIdx.x * blockDim.x + threadIdx.x) * 8;
+       i0 < 2 * pairs_per_tensor; i0 += stride) {
+    T* x = i0 < pairs_per_tensor ? xq : xk;
+    const long i = i0 < pairs_per_tensor ? i0 : i0 - pairs_per_tensor;
+    const long d = i % h2;
+    const long hd = (i / h2) % np;
+    const long si = (i / ((long)h2 * np)) % s;
+    const long bi = i / ((long)h2 * np * s);
+    const long base = bi * sb + hd * sh + si * sr;
+    const float* cr = cos_t + (si + offset) * (2 * h2) + d;
+    const float* sn_r = sin_t + (si + offset) * (2 * h2) + d;
+    float x1[8], x2[8], o1[8], o2[8];
+    load8<T>(x + base + d, x1);
+    load8<T>(x + base + d + h2, x2);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float c = cr[j];
+      const float sn = sn_r[j];
+      if (!BWD) {
+        o1[j] = x1[j] * c - x2[j] * sn;
+        o2[j] = x2[j] * c + x1[j] * sn;
+      } else {  // transpose rotation
+        o1[j] = x1[j] * c + x2[j] * sn;
+        o2[j] = x2[j] * c - x1[j] * sn;
+      }
+    }
+    store8<T>(x + base + d, o1);
+    store8<T>(x + base + d + h2, o2);
+  }
+}
+
 // ===========================================================================
 // SwiGLU: packed [rows, 2h] -> out [rows, h]
 // ===========================================================================
@@ -795,6 +841,25 @@ void fs_rope(const void* x, void* out, const float* cos_t, const float* sin_t,
       hipLaunchKernelGGL((rope_kernel<T, false>), dim3(grid), dim3(256), 0, s,
                          (const T*)x, (T*)out, cos_t, sin_t, total_pairs, seq,
                          h2, offset);
+  });
+}
+
+void fs_rope_inplace(void* xq, void* xk, const float* cos_t,
+                     const float* sin_t, int b, int np, int seq, int hn,
+                     long sb, long sh, long sr, int offset, int bwd,
+                     int dtype, hipStream_t s) {
+  const int h2 = hn / 2;
+  const long per_tensor = (long)b * np * seq * h2;
+  int grid = grid_for(2 * per_tensor / 8);
+  DISPATCH_DTYPE(dtype, T, {
+    if (bwd)
+      hipLaunchKernelGGL((rope_inplace_kernel<T, true>), dim3(grid),
+                         dim3(256), 0, s, (T*)xq, (T*)xk, cos_t, sin_t,
+                         per_tensor, np, seq, h2, offset, sb, sh, sr);
+    else
+      hipLaunchKernelGGL((rope_inplace_kernel<T, false>), dim3(grid),
+                         dim3(256), 0, s, (T*)xq, (T*)xk, cos_t, sin_t,
+                         per_tensor, np, seq, h2, offset, sb, sh, sr);
   });
 }
 

@@ -73,6 +73,121 @@ class _FlashAttention(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None, None
 
 
+def _thirds(qkv, num_heads):
+    """[b, s, >=3*np*hn] packed buffer -> q, k, v as [b, np, s, hn] views."""
+    h = qkv.shape[-1] // 3
+    return tuple(qkv.narrow(2, i * h, h).unflatten(2, (num_heads, -1))
+                 .transpose(1, 2) for i in range(3))
+
+
+class _RopePackedInplace(torch.autograd.Function):
+    """Rotates the q and k thirds of a packed [b, s, 3*np*hn] buffer in
+    place and returns it marked dirty, so autograd sees the overwrite (no
+    linear backward needs its own output, so overwriting the projection
+    output is sound).  A function of its own because autograd allows an
+    in-place update of a view input (a biased linear's output is one) only
+    in a Function with a single output."""
+
+    @staticmethod
+    def forward(ctx, qkv, num_heads, cos, sin, offset):
+        q, k, _ = _thirds(qkv, num_heads)
+        get_ext().rope_inplace(q, k, cos, sin, offset, False)
+        ctx.mark_dirty(qkv)
+        ctx.save_for_backward(cos, sin)
+        ctx.num_heads = num_heads
+        ctx.offset = offset
+        return qkv
+
+    @staticmethod
+    def backward(ctx, grad):
+        cos, sin = ctx.saved_tensors
+        # rotation is orthogonal: un-rotate the q/k thirds.  Done in place:
+        # packed_self_attention never lets the rotated buffer escape, so
+        # its only consumer is _PackedFlash, whose backward allocates this
+        # gradient fresh and keeps no reference to it.
+        if grad.stride(-1) != 1 or any(st % 8 for st in grad.stride()[:-1]) \
+                or grad.storage_offset() % 8:
+            grad = grad.contiguous()
+        dq, dk, _ = _thirds(grad, ctx.num_heads)
+        get_ext().rope_inplace(dq, dk, cos, sin, ctx.offset, True)
+        return grad, None, None, None, None
+
+
+class _PackedFlash(torch.autograd.Function):
+    """v3 flash attention straight on the packed QKV buffer: the strided
+    kernels read the three thirds where the GEMM left them and write O as
+    [b, s, np*hn]; backward writes dq/dk/dv into the thirds of one packed
+    gradient.  No layout copies, no ``cat``."""
+
+    @staticmethod
+    def forward(ctx, qkv, num_heads, scale, causal, klens):
+        b, s, w = qkv.shape
+        q, k, v = _thirds(qkv, num_heads)
+        o = torch.empty(b, s, w // 3, dtype=qkv.dtype, device=qkv.device)
+        lse = get_ext().flash_attn_fwd_v3_strided(
+            q, k, v, o.unflatten(2, (num_heads, -1)).transpose(1, 2), scale,
+            causal, klens)
+        ctx.save_for_backward(qkv, o, lse)
+        ctx.num_heads = num_heads
+        ctx.scale = scale
+        ctx.causal = causal
+        ctx.klens = klens
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, o, lse = ctx.saved_tensors
+        np_ = ctx.num_heads
+        q, k, v = _thirds(qkv, np_)
+        # dO is read where it lies as long as its last dim is contiguous
+        if do.stride(-1) != 1 or any(st % 8 for st in do.stride()[:-1]) \
+                or do.storage_offset() % 8:
+            do = do.contiguous()
+        grad = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
+        dq, dk, dv = _thirds(grad, np_)
+        get_ext().flash_attn_bwd_v3_strided(
+            q, k, v, o.unflatten(2, (np_, -1)).transpose(1, 2),
+            do.unflatten(2, (np_, -1)).transpose(1, 2), lse, dq, dk, dv,
+            ctx.scale, ctx.causal, ctx.klens)
+        return grad, None, None, None, None
+
+
+def packed_attn_eligible(qkv, head_dim: int, causal: bool, mask,
+                         dropout_p: float) -> bool:
+    """True when self-attention can run on the packed [b, s, 3*np*hn]
+    projection output in place: v3 shapes (d in {64, 96, 128}, s % 64 == 0),
+    bf16, no dropout, and no mask under causal (a bidirectional mask must
+    still reduce to klens — checked by the caller).  FENGSHEN_PACKED_ATTN=0
+    forces the chunk/transpose/contiguous path."""
+    import os
+    if os.environ.get("FENGSHEN_PACKED_ATTN", "1") == "0":
+        return False
+    if qkv.dtype != torch.bfloat16 or qkv.dim() != 3 or dropout_p > 0:
+        return False
+    s = qkv.shape[1]
+    if head_dim not in (64, 96, 128) or s % 64 != 0 or s < 64:
+        return False
+    if causal and mask is not None:
+        return False
+    return (qkv.stride(2) == 1 and qkv.stride(0) % 8 == 0
+            and qkv.stride(1) % 8 == 0 and qkv.storage_offset() % 8 == 0)
+
+
+def packed_self_attention(qkv: torch.Tensor, num_heads: int,
+                          cos: Optional[torch.Tensor],
+                          sin: Optional[torch.Tensor], offset: int,
+                          scale: float, causal: bool = True,
+                          klens: Optional[torch.Tensor] = None
+                          ) -> torch.Tensor:
+    """qkv [b, s, 3*np*hn] bf16, partition-local layout [q | k | v], last dim
+    unit-stride.  Rotates q/k IN PLACE when cos/sin are given (pass None
+    for no rotary) and returns the context as [b, s, np*hn], ready for the
+    output projection.  Callers must not reuse ``qkv`` afterwards."""
+    if cos is not None:
+        qkv = _RopePackedInplace.apply(qkv, num_heads, cos, sin, offset)
+    return _PackedFlash.apply(qkv, num_heads, float(scale), causal, klens)
+
+
 def _draw_seed(device) -> int:
     """Per-call dropout seed: CPU torch RNG (deterministic under
     torch.manual_seed) mixed with the TP rank so TP-local heads get
