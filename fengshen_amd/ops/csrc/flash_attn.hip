@@ -984,9 +984,12 @@ extern "C" void fs_flash_attn_bwd(const void* q, const void* k, const void* v,
 //     registers, so the row max/sum are 31 in-lane ops + one cross-half
 //     shuffle — no 4-round shuffle-reduce trees, and softmax state m/l is
 //     a per-lane scalar;
-//   - P crosses to the PV A-operand through a per-wave LDS exchange
-//     (bf16, 8B stores / 16B reads).
-// Layouts verified on HW by scripts/mfma32_probe.hip.
+//   - P reaches the PV A-operand in registers (cvt-pack + permlane32_swap);
+//   - V is staged row-major once and read column-wise with the transposed
+//     LDS read (no second, transposed image);
+//   - causal: a wave skips the tiles that lie wholly above its q rows.
+// Layouts verified on HW by scripts/mfma32_probe.hip and
+// scripts/ds_read_tr_probe.hip.
 
 #define V3_QBLK 256          // 8 waves x 32 q rows
 #define V3_KVBLK 64
@@ -1002,6 +1005,79 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 struct FaStrides {
   long b, h, r;
 };
+
+// ---- one LDS image per streamed tile, read by rows AND by columns --------
+// A streamed tile (K, V, Q, dO) is staged once, row-major, with 16-byte
+// stores.  MFMAs that want its rows read 16-byte chunks (ds_read_b128);
+// MFMAs that want its columns (V in P.V, K in dS.K, dO in Pt.dO, Q in dSt.Q)
+// use the gfx950 transposed read ds_read_b64_tr_b16: per 16-lane group,
+// lane i supplies the address of row i>>2, columns 4*(i&3)..+3 of a 4-row x
+// 16-column block and receives column i of it, row q in element q (verified
+// on HW by scripts/ds_read_tr_probe.hip).  The read gathers across lanes, so
+// EXEC must be all ones: every call sits in wave-uniform control flow, and
+// inactive waves compute on clamped rows instead of being masked off.
+typedef __attribute__((ext_vector_type(4))) short bf16x4;
+typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+
+// Byte offset of 16-byte chunk `ch` of row `row`.  SWB (row stride in bytes)
+// is 256 for D = 128 / 96 and 128 for D = 64.  The chunk XOR keeps the
+// staging store, the row read and the transposed read of the 32x32x16
+// operands free of bank conflicts (64 banks of 4 B for the reads, 32 for
+// the store); it only uses row bits 0..3, so tiles of 16-row multiples
+// share one per-lane address.
+template <int SWB>
+__device__ __forceinline__ int v3_off(int row, int ch) {
+  static_assert(SWB == 256 || SWB == 128, "row stride");
+  if (SWB == 256)
+    return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
+  return 128 * row + 16 * (ch ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3)));
+}
+
+// This lane's address for the transposed read of the 4-row block at row0 of
+// the 32 columns starting at col0 (lanes 0-15 and 32-47 take columns
+// col0..+15, the others col0+16..+31).
+template <int SWB>
+__device__ __forceinline__ int v3_tr_addr(int lane, int row0, int col0) {
+  const int i = lane & 15;
+  const int col = col0 + 16 * ((lane >> 4) & 1) + 4 * (i & 3);
+  return v3_off<SWB>(row0 + (i >> 2), col >> 3) + 2 * (col & 7);
+}
+
+// B fragment of mfma_f32_32x32x16_bf16 (element j = X[k0 + 8*hi + j][col0 +
+// ln]) from a row-major image; a0 / a1 = v3_tr_addr of rows k0 + 8*hi and
+// k0 + 8*hi + 4.  The same call yields the A fragment of X^T.
+__device__ __forceinline__ bf16x8 v3_tr_frag(const char* a0, const char* a1) {
+  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)a0);
+  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)a1);
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// B fragment for d columns 32*t + ln of the 16 rows at `rows`, from one
+// per-lane base tbase = v3_tr_addr(lane, 8*hi, 0): tile t flips chunk bits
+// 2..3 (byte bits 6..7) and the second 4-row block flips chunk bit 0, so
+// the other addresses are one XOR away and need no registers of their own.
+template <int SWB>
+__device__ __forceinline__ bf16x8 v3_tr_bfrag(const char* rows, int tbase,
+                                              int t) {
+  const int a0 = tbase ^ (64 * t);
+  return v3_tr_frag(rows + a0, rows + (a0 ^ 16) + 4 * SWB);
+}
+
+// Wait for this wave's LDS traffic only (lgkmcnt(0); vmcnt and expcnt left
+// at their maxima).  The per-wave exchanges use it instead of a full
+// s_waitcnt 0, which would also wait for the next tile's global prefetch.
+__device__ __forceinline__ void v3_wait_lds() {
+  __builtin_amdgcn_s_waitcnt(0xC07F);
+}
+
+// dkv exchange image, [32 rows][32 x 16-bit] with 64-byte rows: byte offset
+// of 8-byte unit u of `row`.  The 16 lanes of one ds_write_b64 group store
+// the same unit of 16 consecutive rows; the XOR spreads them over all 32
+// store banks.  A transposed read takes 4 whole rows (256 contiguous bytes)
+// per 32-lane half, conflict-free under any unit permutation.
+__device__ __forceinline__ int dkv_xoff(int row, int u) {
+  return 64 * row + 8 * (u ^ ((row >> 1) & 7));
+}
 
 // delta[b,h,s] = rowsum(dO * O) over strided rows; same per-row arithmetic
 // as flash_delta_kernel.  Grid (x, h, b): blockIdx.y/z pick the head and
@@ -1048,8 +1124,10 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
   constexpr int NTO = D / 32;    // 32-wide output d-tiles
   constexpr int SWB = fa_swb(D);
 
-  __shared__ char k_raw[2][V3_KVBLK * SWB];             // swizzled K rows
-  __shared__ short vt_lds[2][D][V3_KVBLK + FA_VPAD];    // V transposed
+  __shared__ __attribute__((aligned(16)))
+  char k_raw[2][V3_KVBLK * SWB];                        // swizzled K rows
+  __shared__ __attribute__((aligned(16)))
+  char v_raw[2][V3_KVBLK * SWB];    // V rows (v3_off), read transposed
   // (double-buffered: tile t+1 stages into buf^1 while buf holds tile t,
   // so the loop needs ONE barrier per tile instead of two.
   // P stays fully in registers via cvt-pack + permlane32_swap — T12;
@@ -1132,13 +1210,20 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
         const int kc = i % D;
         *reinterpret_cast<bf16x8*>(
             k_raw[0] + kr * SWB + kswz(kr, kc * 2)) = k_reg[sweep];
-        bf16x8 vv = v_reg[sweep];
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          vt_lds[0][kc + j][kr ^ ((kc + j) & 0x38)] = vv[j];
+        *reinterpret_cast<bf16x8*>(
+            v_raw[0] + v3_off<SWB>(kr, kc >> 3)) = v_reg[sweep];
       }
     }
   }
+  // transposed-read base: V rows 8*hi.., d columns ln (v3_tr_bfrag); kv
+  // chunk c2 adds 16 rows, which leaves the swizzle term unchanged
+  const int v_tr = v3_tr_addr<SWB>(lane, 8 * hi, 0);
+  // causal: a wave whose last q row lies above a tile sees only masked
+  // entries there (P = 0 exactly, m/l unchanged) and skips the compute
+  // part; staging and the barrier stay unconditional.  The test is on the
+  // wave's first lane so the branch is scalar and EXEC stays full.
+  const int q_last_w = __builtin_amdgcn_readfirstlane(q0c) + 31;
+
   int cur = 0;
   for (int kt = 0; kt < n_kv_tiles; ++kt) {
     const int k_base = kt * V3_KVBLK;
@@ -1157,130 +1242,131 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
       }
     }
 
-    // ---- S^T = K_tile @ (sQ)^T : two 32x32 kv-tiles ---------------------
-    f32x16 st[2];
+    if (!CAUSAL || k_base <= q_last_w) {
+      // ---- S^T = K_tile @ (sQ)^T : two 32x32 kv-tiles ---------------------
+      f32x16 st[2];
 #pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
+      for (int nt = 0; nt < 2; ++nt) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) st[nt][r] = 0.f;
-    }
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      const int krow = nt * 32 + ln;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        bf16x8 a = *reinterpret_cast<const bf16x8*>(
-            k_raw[cur] + krow * SWB + kswz(krow, (c * 16 + hi * 8) * 2));
-        st[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, q_frag[c],
-                                                         st[nt], 0, 0, 0);
+        for (int r = 0; r < 16; ++r) st[nt][r] = 0.f;
       }
-    }
-    // lane now holds S^T[kv][q = my row]: kv = k_base + nt*32 + crow(r,hi)
-    // with crow(r,hi) = (r&3) + 8*(r>>2) + 4*hi
-
-    // ---- causal mask + in-register online softmax ----------------------
-    float p[32];
-    float tmax = -INFINITY;
 #pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
+      for (int nt = 0; nt < 2; ++nt) {
+        const int krow = nt * 32 + ln;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int kcol = k_base + nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-        float v = st[nt][r];
-        if (CAUSAL ? (kcol > my_q) : (kcol >= klen)) v = -INFINITY;
-        p[nt * 16 + r] = v;
-        tmax = fmaxf(tmax, v);
+        for (int c = 0; c < NC; ++c) {
+          bf16x8 a = *reinterpret_cast<const bf16x8*>(
+              k_raw[cur] + krow * SWB + kswz(krow, (c * 16 + hi * 8) * 2));
+          st[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, q_frag[c],
+                                                           st[nt], 0, 0, 0);
+        }
       }
-    }
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));  // combine lane halves
-    const float m_new = fmaxf(m_run, tmax);
-    const float alpha = (m_run == -INFINITY) ? 0.f : __expf(m_run - m_new);
-    const bool rescale = (m_new != m_run);
-    m_run = m_new;
-    float rs = 0.f;
-#pragma unroll
-    for (int i = 0; i < 32; ++i) {
-      float e = (p[i] == -INFINITY) ? 0.f : __expf(p[i] - m_new);
-      p[i] = e;
-      rs += e;
-    }
-    rs += __shfl_xor(rs, 32, 64);
-    l_run = l_run * alpha + rs;
+      // lane now holds S^T[kv][q = my row]: kv = k_base + nt*32 + crow(r,hi)
+      // with crow(r,hi) = (r&3) + 8*(r>>2) + 4*hi
 
-    // attention dropout on P (normalizer keeps the undropped sum)
-    if (HAS_DROP && drop_thresh) {
-      const unsigned long long qi =
-          (bh * (unsigned long long)s + my_q) * (unsigned long long)s;
+      // ---- causal mask + in-register online softmax ----------------------
+      float p[32];
+      float tmax = -INFINITY;
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int kcol =
-              k_base + nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          float& pv = p[nt * 16 + r];
-          pv = (fa_hash(drop_seed, qi + kcol) < drop_thresh)
-                   ? 0.f : pv * keep_scale;
+          const int kcol = k_base + nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+          float v = st[nt][r];
+          if (CAUSAL ? (kcol > my_q) : (kcol >= klen)) v = -INFINITY;
+          p[nt * 16 + r] = v;
+          tmax = fmaxf(tmax, v);
         }
       }
-    }
+      tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));  // combine lane halves
+      const float m_new = fmaxf(m_run, tmax);
+      const float alpha = (m_run == -INFINITY) ? 0.f : __expf(m_run - m_new);
+      const bool rescale = (m_new != m_run);
+      m_run = m_new;
+      float rs = 0.f;
+#pragma unroll
+      for (int i = 0; i < 32; ++i) {
+        float e = (p[i] == -INFINITY) ? 0.f : __expf(p[i] - m_new);
+        p[i] = e;
+        rs += e;
+      }
+      rs += __shfl_xor(rs, 32, 64);
+      l_run = l_run * alpha + rs;
 
-    // rescale: alpha for o-row crow(r,hi) fetched by lane shuffle
-    // (alpha is per-q-row, identical in lanes l and l+32)
-    if (__any(rescale)) {
+      // attention dropout on P (normalizer keeps the undropped sum)
+      if (HAS_DROP && drop_thresh) {
+        const unsigned long long qi =
+            (bh * (unsigned long long)s + my_q) * (unsigned long long)s;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float al = __shfl(alpha, (r & 3) + 8 * (r >> 2) + 4 * hi, 64);
+        for (int nt = 0; nt < 2; ++nt) {
 #pragma unroll
-        for (int t = 0; t < NTO; ++t) o_acc[t][r] *= al;
+          for (int r = 0; r < 16; ++r) {
+            const int kcol =
+                k_base + nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+            float& pv = p[nt * 16 + r];
+            pv = (fa_hash(drop_seed, qi + kcol) < drop_thresh)
+                     ? 0.f : pv * keep_scale;
+          }
+        }
       }
-    }
 
-    // ---- P -> A-fragments in registers (T12) ----------------------------
-    // Lane layout: p holds, for its own q row, kv octs G = 4*nt + g with
-    // 4-runs at kv = 8G + 4*hi + j.  A-frag for PV chunk c2 needs kv
-    // 16c2 + 8*hi' + j: word pair k from oct 2c2 (hi=0 half) and oct
-    // 2c2+1 (hi=1 half).  One permlane32_swap per word yields BOTH
-    // halves' targets: out0 = words 0/1, out1 = words 2/3, uniformly.
-    unsigned int pw[8][2];  // [oct][word]: packed bf16 pairs of own run
+      // rescale: alpha for o-row crow(r,hi) fetched by lane shuffle
+      // (alpha is per-q-row, identical in lanes l and l+32)
+      if (__any(rescale)) {
 #pragma unroll
-    for (int G = 0; G < 8; ++G) {
-      const int base = (G >> 2) * 16 + (G & 3) * 4;
+        for (int r = 0; r < 16; ++r) {
+          const float al = __shfl(alpha, (r & 3) + 8 * (r >> 2) + 4 * hi, 64);
 #pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const unsigned int lo =
-            (unsigned short)fa_bf16bits(p[base + 2 * k]);
-        const unsigned int hi_b =
-            (unsigned short)fa_bf16bits(p[base + 2 * k + 1]);
-        pw[G][k] = (hi_b << 16) | lo;
+          for (int t = 0; t < NTO; ++t) o_acc[t][r] *= al;
+        }
       }
-    }
 
-    // ---- PV: O[q][d] += P[q][kv] @ V[kv][d] -----------------------------
+      // ---- P -> A-fragments in registers (T12) ----------------------------
+      // Lane layout: p holds, for its own q row, kv octs G = 4*nt + g with
+      // 4-runs at kv = 8G + 4*hi + j.  A-frag for PV chunk c2 needs kv
+      // 16c2 + 8*hi' + j: word pair k from oct 2c2 (hi=0 half) and oct
+      // 2c2+1 (hi=1 half).  One permlane32_swap per word yields BOTH
+      // halves' targets: out0 = words 0/1, out1 = words 2/3, uniformly.
+      unsigned int pw[8][2];  // [oct][word]: packed bf16 pairs of own run
 #pragma unroll
-    for (int c2 = 0; c2 < 4; ++c2) {  // kv chunks of 16
-      unsigned int paw[4];
+      for (int G = 0; G < 8; ++G) {
+        const int base = (G >> 2) * 16 + (G & 3) * 4;
 #pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        auto pr = __builtin_amdgcn_permlane32_swap(
-            (int)pw[2 * c2][k], (int)pw[2 * c2 + 1][k], false, false);
-        paw[k] = (unsigned int)pr[0];
-        paw[k + 2] = (unsigned int)pr[1];
+        for (int k = 0; k < 2; ++k) {
+          const unsigned int lo =
+              (unsigned short)fa_bf16bits(p[base + 2 * k]);
+          const unsigned int hi_b =
+              (unsigned short)fa_bf16bits(p[base + 2 * k + 1]);
+          pw[G][k] = (hi_b << 16) | lo;
+        }
       }
-      bf16x8 pa;
+
+      // ---- PV: O[q][d] += P[q][kv] @ V[kv][d] -----------------------------
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        pa[2 * k] = (short)(paw[k] & 0xFFFF);
-        pa[2 * k + 1] = (short)(paw[k] >> 16);
-      }
+      for (int c2 = 0; c2 < 4; ++c2) {  // kv chunks of 16
+        unsigned int paw[4];
 #pragma unroll
-      for (int t = 0; t < NTO; ++t) {   // d cols, 32 each
-        const int dcol = t * 32 + ln;
-        bf16x8 vb = *reinterpret_cast<const bf16x8*>(
-            &vt_lds[cur][dcol][(c2 * 16 + hi * 8) ^ (dcol & 0x38)]);
-        o_acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, vb, o_acc[t],
-                                                           0, 0, 0);
+        for (int k = 0; k < 2; ++k) {
+          auto pr = __builtin_amdgcn_permlane32_swap(
+              (int)pw[2 * c2][k], (int)pw[2 * c2 + 1][k], false, false);
+          paw[k] = (unsigned int)pr[0];
+          paw[k + 2] = (unsigned int)pr[1];
+        }
+        bf16x8 pa;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          pa[2 * k] = (short)(paw[k] & 0xFFFF);
+          pa[2 * k + 1] = (short)(paw[k] >> 16);
+        }
+#pragma unroll
+        for (int t = 0; t < NTO; ++t) {   // d cols, 32 each
+          const char* vrow = v_raw[cur] + c2 * 16 * SWB;
+          bf16x8 vb = v3_tr_bfrag<SWB>(vrow, v_tr, t);
+          o_acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, vb, o_acc[t],
+                                                             0, 0, 0);
+        }
       }
-    }
+    }  // tile visible to this wave
 
     // stage tile kt+1 into the spare buffer (loop-top barrier publishes)
     if (kt + 1 < n_kv_tiles) {
@@ -1293,10 +1379,8 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
           const int kc = i % D;
           *reinterpret_cast<bf16x8*>(
               k_raw[nxt] + kr * SWB + kswz(kr, kc * 2)) = k_reg[sweep];
-          bf16x8 vv = v_reg[sweep];
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            vt_lds[nxt][kc + j][kr ^ ((kc + j) & 0x38)] = vv[j];
+          *reinterpret_cast<bf16x8*>(
+              v_raw[nxt] + v3_off<SWB>(kr, kc >> 3)) = v_reg[sweep];
         }
       }
       cur = nxt;
@@ -1398,9 +1482,11 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
   constexpr int NTO = D / 32;
   constexpr int SWB = fa_swb(D);
 
-  __shared__ char k_raw[B3_FB * SWB];                  // K rows, swizzled
-  __shared__ char v_raw[B3_FB * SWB];                  // V rows, swizzled
-  __shared__ short kt_lds[D][B3_FB + FA_VPAD];         // K^T (kv-swizzled)
+  // double-buffered row images (v3_off): tile t+1 stages into buf^1 while
+  // buf holds tile t, so the loop needs one barrier per tile.  K is read by
+  // rows for S^T and transposed for dS.K; V by rows only.
+  __shared__ __attribute__((aligned(16))) char k_raw[2][B3_FB * SWB];
+  __shared__ __attribute__((aligned(16))) char v_raw[2][B3_FB * SWB];
   __shared__ short p_x[FA_WAVES][32][B3_FB + FA_VPAD];
 
   const int lane = threadIdx.x & 63;
@@ -1457,87 +1543,110 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
     n_kv_tiles = (klen + B3_FB - 1) / B3_FB;
   }
 
+  // staging: one 16-byte chunk of K and of V per thread (B3_FB * D / 8
+  // <= 512 chunks), prefetched into registers under the MFMAs
+  const int st_i = threadIdx.x * 8;
+  const bool st_on = st_i < B3_FB * D;
+  const int st_r = st_on ? st_i / D : 0;
+  const int st_c = st_on ? st_i % D : 0;
+  const int st_off = v3_off<SWB>(st_r, st_c >> 3);
+  bf16x8 k_reg, v_reg;
+  {
+    const long krg = min(st_r, s - 1);
+    k_reg = *reinterpret_cast<const bf16x8*>(Kp + krg * qs.r + st_c);
+    v_reg = *reinterpret_cast<const bf16x8*>(Vp + krg * qs.r + st_c);
+  }
+  if (st_on) {
+    *reinterpret_cast<bf16x8*>(k_raw[0] + st_off) = k_reg;
+    *reinterpret_cast<bf16x8*>(v_raw[0] + st_off) = v_reg;
+  }
+  // transposed-read base (v3_tr_bfrag) and row-read base: chunk 2c + hi of
+  // row ln is the base with byte bits 5.. flipped by c
+  const int k_tr = v3_tr_addr<SWB>(lane, 8 * hi, 0);
+  const int kv_row = v3_off<SWB>(ln, hi);
+  // causal: tiles wholly right of the wave's last q row give dS = 0 exactly;
+  // the wave skips their compute part (scalar branch, EXEC stays full)
+  const int q_last_w = __builtin_amdgcn_readfirstlane(q0c) + 31;
+
+  int cur = 0;
   for (int kt = 0; kt < n_kv_tiles; ++kt) {
     const int k_base = kt * B3_FB;
-    __syncthreads();
-    {
-      const int tid = threadIdx.x;
-      for (int i = tid * 8; i < B3_FB * D; i += FA_WAVES * 64 * 8) {
-        const int kr = i / D;
-        const int kc = i % D;
-        const long krg = min(k_base + kr, s - 1);
-        bf16x8 kk = *reinterpret_cast<const bf16x8*>(Kp + krg * qs.r + kc);
-        *reinterpret_cast<bf16x8*>(k_raw + kr * SWB + kswz(kr, kc * 2)) = kk;
-        bf16x8 vv = *reinterpret_cast<const bf16x8*>(Vp + krg * qs.r + kc);
-        *reinterpret_cast<bf16x8*>(v_raw + kr * SWB + kswz(kr, kc * 2)) = vv;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          kt_lds[kc + j][kr ^ ((kc + j) & 0x18)] = kk[j];
-      }
+    __syncthreads();  // publishes buf[cur]; everyone done with buf[cur^1]
+    if (kt + 1 < n_kv_tiles) {
+      const long krg = min(k_base + B3_FB + st_r, s - 1);
+      k_reg = *reinterpret_cast<const bf16x8*>(Kp + krg * qs.r + st_c);
+      v_reg = *reinterpret_cast<const bf16x8*>(Vp + krg * qs.r + st_c);
     }
-    __syncthreads();
 
-    // S^T = K (sQ)^T and dP^T = V dO^T : one 32x32 kv-tile each
-    f32x16 st, dpt;
+    if (!CAUSAL || k_base <= q_last_w) {
+      // S^T = K (sQ)^T and dP^T = V dO^T : one 32x32 kv-tile each
+      f32x16 st, dpt;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      st[r] = 0.f;
-      dpt[r] = 0.f;
-    }
-    {
-      const int krow = ln;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        bf16x8 ka = *reinterpret_cast<const bf16x8*>(
-            k_raw + krow * SWB + kswz(krow, (c * 16 + hi * 8) * 2));
-        st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, q_frag[c], st,
-                                                     0, 0, 0);
-        bf16x8 va = *reinterpret_cast<const bf16x8*>(
-            v_raw + krow * SWB + kswz(krow, (c * 16 + hi * 8) * 2));
-        dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, do_frag[c], dpt,
-                                                      0, 0, 0);
+      for (int r = 0; r < 16; ++r) {
+        st[r] = 0.f;
+        dpt[r] = 0.f;
       }
-    }
-    // lane holds, for its OWN q row: kv = k_base + crow(r,hi)
-
-    // dS = P * (dP - delta) * scale, in-register; exchange by q row
+      {
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      short pk[4] __attribute__((aligned(8)));
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int r = g * 4 + j;
-        const int kcol = k_base + (r & 3) + 8 * (r >> 2) + 4 * hi;
-        const bool masked = CAUSAL ? (kcol > my_q) : (kcol >= klen);
-        float pv = masked ? 0.f : __expf(st[r] - lse_r);
-        float dpv = dpt[r];
-        if (HAS_DROP && drop_thresh) {
-          const unsigned long long idx =
-              (bh * (unsigned long long)s + my_q) *
-                  (unsigned long long)s + kcol;
-          dpv = (fa_hash(drop_seed, idx) < drop_thresh)
-                    ? 0.f : dpv * keep_scale;
+        for (int c = 0; c < NC; ++c) {
+          const int roff = kv_row ^ (32 * c);
+          bf16x8 ka = *reinterpret_cast<const bf16x8*>(k_raw[cur] + roff);
+          st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, q_frag[c], st,
+                                                       0, 0, 0);
+          bf16x8 va = *reinterpret_cast<const bf16x8*>(v_raw[cur] + roff);
+          dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, do_frag[c], dpt,
+                                                        0, 0, 0);
         }
-        pk[j] = fa_bf16bits(pv * (dpv - dlt_r) * scale);
       }
-      *reinterpret_cast<long*>(&p_x[wave][ln][8 * g + 4 * hi]) =
-          *reinterpret_cast<const long*>(pk);
-    }
-    __builtin_amdgcn_s_waitcnt(0);
+      // lane holds, for its OWN q row: kv = k_base + crow(r,hi)
 
-    // dQ += dS @ K : A = dS [32q x 16kv], B = K^T
+      // dS = P * (dP - delta) * scale, in-register; exchange by q row
 #pragma unroll
-    for (int c2 = 0; c2 < 2; ++c2) {
-      bf16x8 pa = *reinterpret_cast<const bf16x8*>(
-          &p_x[wave][ln][c2 * 16 + hi * 8]);
+      for (int g = 0; g < 4; ++g) {
+        short pk[4] __attribute__((aligned(8)));
 #pragma unroll
-      for (int t = 0; t < NTO; ++t) {
-        const int dcol = t * 32 + ln;
-        bf16x8 kb = *reinterpret_cast<const bf16x8*>(
-            &kt_lds[dcol][(c2 * 16 + hi * 8) ^ (dcol & 0x18)]);
-        dq_acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, kb,
-                                                            dq_acc[t],
-                                                            0, 0, 0);
+        for (int j = 0; j < 4; ++j) {
+          const int r = g * 4 + j;
+          const int kcol = k_base + (r & 3) + 8 * (r >> 2) + 4 * hi;
+          const bool masked = CAUSAL ? (kcol > my_q) : (kcol >= klen);
+          float pv = masked ? 0.f : __expf(st[r] - lse_r);
+          float dpv = dpt[r];
+          if (HAS_DROP && drop_thresh) {
+            const unsigned long long idx =
+                (bh * (unsigned long long)s + my_q) *
+                    (unsigned long long)s + kcol;
+            dpv = (fa_hash(drop_seed, idx) < drop_thresh)
+                      ? 0.f : dpv * keep_scale;
+          }
+          pk[j] = fa_bf16bits(pv * (dpv - dlt_r) * scale);
+        }
+        *reinterpret_cast<long*>(&p_x[wave][ln][8 * g + 4 * hi]) =
+            *reinterpret_cast<const long*>(pk);
+      }
+      v3_wait_lds();
+
+      // dQ += dS @ K : A = dS [32q x 16kv], B = K read transposed
+#pragma unroll
+      for (int c2 = 0; c2 < 2; ++c2) {
+        bf16x8 pa = *reinterpret_cast<const bf16x8*>(
+            &p_x[wave][ln][c2 * 16 + hi * 8]);
+        const char* krows = k_raw[cur] + c2 * 16 * SWB;
+#pragma unroll
+        for (int t = 0; t < NTO; ++t) {
+          bf16x8 kb = v3_tr_bfrag<SWB>(krows, k_tr, t);
+          dq_acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, kb,
+                                                              dq_acc[t],
+                                                              0, 0, 0);
+        }
+      }
+    }  // tile visible to this wave
+
+    // stage tile kt+1 into the spare buffer (loop-top barrier publishes)
+    if (kt + 1 < n_kv_tiles) {
+      cur ^= 1;
+      if (st_on) {
+        *reinterpret_cast<bf16x8*>(k_raw[cur] + st_off) = k_reg;
+        *reinterpret_cast<bf16x8*>(v_raw[cur] + st_off) = v_reg;
       }
     }
   }
@@ -1553,9 +1662,9 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
 }
 
 // KV-major: wave owns 32 kv rows (block 256), streams Q/dO in 32-tiles.
-// VGPR budget forces a T16-style time-share: the wave's own K rows load
-// into a register block for the St MFMAs, then V overwrites the same
-// block for the dPt MFMAs (rows are L2-hot; the loads hide under MFMA).
+// The wave's own K and V rows stay in registers for the whole loop (64
+// VGPRs next to the 128 of dK/dV), which puts the kernel at the 256-VGPR
+// cap: a few loop-invariant values live in scratch.
 // The softmax scale folds into the exp (st*scale - lse) so K stays raw.
 template <int D, bool CAUSAL, bool HAS_DROP>
 __global__ __launch_bounds__(FA_WAVES * 64)
@@ -1576,12 +1685,19 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
   constexpr int NTO = D / 32;
   constexpr int SWB = fa_swb(D);
 
-  __shared__ char q_raw[B3_FB * SWB];                   // Q rows, swizzled
-  __shared__ char do_raw[B3_FB * SWB];                  // dO rows, swizzled
-  __shared__ short qt_lds[D][B3_FB + FA_VPAD];          // Q^T
-  __shared__ short dot_lds[D][B3_FB + FA_VPAD];         // dO^T
-  __shared__ short p_x[FA_WAVES][32][B3_FB + FA_VPAD];   // Pt by kv row
-  __shared__ short ds_x[FA_WAVES][32][B3_FB + FA_VPAD];  // dSt by kv row
+  // row images (v3_off): Q and dO are read by rows for St / dPt and
+  // transposed for dSt.Q / Pt.dO.  Single-buffered, two barriers per tile:
+  // this kernel sits at the 256-VGPR cap, and the registers a prefetched
+  // tile needs turn into scratch traffic that costs more than the overlap
+  // gains (docs/KERNELS.md, negative results)
+  __shared__ __attribute__((aligned(16))) char q_raw[B3_FB * SWB];
+  __shared__ __attribute__((aligned(16))) char do_raw[B3_FB * SWB];
+  // per-wave exchange of Pt / dSt, held as [q column][kv row] with 64-byte
+  // rows: a lane stores its q column's kv runs 8g + 4*hi .. +3 as 8-byte
+  // units (unit XOR dkv_xoff: conflict-free stores) and the A operand
+  // [kv row][q] comes back through the transposed read
+  __shared__ __attribute__((aligned(16))) char p_x[FA_WAVES][32 * 64];
+  __shared__ __attribute__((aligned(16))) char ds_x[FA_WAVES][32 * 64];
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -1620,90 +1736,119 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
   const int first_qt = CAUSAL ? kv0_blk / B3_FB : 0;
   const int n_q_tiles = s / B3_FB;
 
+  // staging: one 16-byte chunk of Q and of dO per thread (B3_FB * D / 8
+  // <= 512 chunks)
+  const int st_i = threadIdx.x * 8;
+  const bool st_on = st_i < B3_FB * D;
+  const int st_r = st_on ? st_i / D : 0;
+  const int st_c = st_on ? st_i % D : 0;
+  const int st_off = v3_off<SWB>(st_r, st_c >> 3);
+  // transposed-read base (v3_tr_bfrag) and row-read base: chunk 2c + hi of
+  // row ln is the base with byte bits 5.. flipped by c
+  const int qd_tr = v3_tr_addr<SWB>(lane, 8 * hi, 0);
+  const int qd_row = v3_off<SWB>(ln, hi);
+  // exchange image: rows q 8*hi (+4) + (i>>2), kv columns = this lane's ln
+  int x_tr[2];
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const int i = lane & 15;
+    const int row = 8 * hi + 4 * e + (i >> 2);
+    x_tr[e] = dkv_xoff(row, 4 * ((lane >> 4) & 1) + (i & 3));
+  }
+  // the wave's own K and V rows as A fragments, loaded once: they do not
+  // change from tile to tile.  (The compiler used to hoist these loads out
+  // of the loop by itself; anything that keeps it from doing so, such as a
+  // branch around them, leaves 16 loads of 32 B per row in every tile of
+  // every wave and makes the kernel L2-bound, 1.5x slower.)
+  bf16x8 k_frag[NC], v_frag[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    k_frag[c] = *reinterpret_cast<const bf16x8*>(
+        Kp + (long)my_kv * qs.r + c * 16 + hi * 8);
+    v_frag[c] = *reinterpret_cast<const bf16x8*>(
+        Vp + (long)my_kv * qs.r + c * 16 + hi * 8);
+  }
+
   for (int qt = first_qt; qt < n_q_tiles; ++qt) {
     const int q_base = qt * B3_FB;
     __syncthreads();
     {
-      const int tid = threadIdx.x;
-      for (int i = tid * 8; i < B3_FB * D; i += FA_WAVES * 64 * 8) {
-        const int qr = i / D;
-        const int qc = i % D;
-        bf16x8 qq = *reinterpret_cast<const bf16x8*>(
-            Qp + (long)(q_base + qr) * qs.r + qc);
-        *reinterpret_cast<bf16x8*>(q_raw + qr * SWB + kswz(qr, qc * 2)) = qq;
-        bf16x8 dd = *reinterpret_cast<const bf16x8*>(
-            dOp + (long)(q_base + qr) * dos.r + qc);
-        *reinterpret_cast<bf16x8*>(do_raw + qr * SWB + kswz(qr, qc * 2)) =
-            dd;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          qt_lds[qc + j][qr ^ ((qc + j) & 0x18)] = qq[j];
-          dot_lds[qc + j][qr ^ ((qc + j) & 0x18)] = dd[j];
-        }
+      const long qrg = q_base + st_r;
+      const bf16x8 qq =
+          *reinterpret_cast<const bf16x8*>(Qp + qrg * qs.r + st_c);
+      const bf16x8 dd =
+          *reinterpret_cast<const bf16x8*>(dOp + qrg * dos.r + st_c);
+      if (st_on) {
+        *reinterpret_cast<bf16x8*>(q_raw + st_off) = qq;
+        *reinterpret_cast<bf16x8*>(do_raw + st_off) = dd;
       }
     }
+    const int qcol = q_base + ln;
+    const float lse_c = lse[qcol];
+    const float dlt_c = dlt[qcol];
     __syncthreads();
 
     // St = K Q^T (raw K; scale folded into the exp below)
-    f32x16 st;
+    f32x16 st, dpt;
 #pragma unroll
     for (int r = 0; r < 16; ++r) st[r] = 0.f;
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-      bf16x8 ka = *reinterpret_cast<const bf16x8*>(
-          Kp + (long)my_kv * qs.r + c * 16 + hi * 8);
       bf16x8 qb = *reinterpret_cast<const bf16x8*>(
-          q_raw + ln * SWB + kswz(ln, (c * 16 + hi * 8) * 2));
-      st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qb, st, 0, 0, 0);
+          q_raw + (qd_row ^ (32 * c)));
+      st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k_frag[c], qb, st, 0, 0,
+                                                   0);
     }
-    // dPt = V dO^T (same register pattern, V overwrites K's slots)
-    f32x16 dpt;
+    // dPt = V dO^T
 #pragma unroll
     for (int r = 0; r < 16; ++r) dpt[r] = 0.f;
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-      bf16x8 va = *reinterpret_cast<const bf16x8*>(
-          Vp + (long)my_kv * qs.r + c * 16 + hi * 8);
       bf16x8 db = *reinterpret_cast<const bf16x8*>(
-          do_raw + ln * SWB + kswz(ln, (c * 16 + hi * 8) * 2));
-      dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, db, dpt, 0, 0, 0);
+          do_raw + (qd_row ^ (32 * c)));
+      dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v_frag[c], db, dpt, 0, 0,
+                                                    0);
     }
-
-    const int qcol = q_base + ln;
-    const float lse_c = lse[qcol];
-    const float dlt_c = dlt[qcol];
 
     // Pt AND dSt by kv row, one exchange pass: st/dpt registers die
     // here (keeping them through the dV MFMAs spilled 128 B/lane)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int kvrow_loc = (r & 3) + 8 * (r >> 2) + 4 * hi;
-      const int kvrow = kv0c + kvrow_loc;
-      const bool masked = CAUSAL ? (qcol < kvrow) : (kvrow >= klen);
-      float pv = masked ? 0.f : __expf(st[r] * scale - lse_c);
-      float dm = 1.f;
-      if (HAS_DROP && drop_thresh) {
-        const unsigned long long idx =
-            (bh * (unsigned long long)s + qcol) *
-                (unsigned long long)s + kvrow;
-        dm = (fa_hash(drop_seed, idx) < drop_thresh) ? 0.f : keep_scale;
+    for (int g = 0; g < 4; ++g) {
+      short pk[4] __attribute__((aligned(8)));
+      short dk4[4] __attribute__((aligned(8)));
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int r = g * 4 + j;
+        const int kvrow = kv0c + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const bool masked = CAUSAL ? (qcol < kvrow) : (kvrow >= klen);
+        float pv = masked ? 0.f : __expf(st[r] * scale - lse_c);
+        float dm = 1.f;
+        if (HAS_DROP && drop_thresh) {
+          const unsigned long long idx =
+              (bh * (unsigned long long)s + qcol) *
+                  (unsigned long long)s + kvrow;
+          dm = (fa_hash(drop_seed, idx) < drop_thresh) ? 0.f : keep_scale;
+        }
+        pk[j] = fa_bf16bits(pv * dm);  // dropped P -> dV
+        dk4[j] = fa_bf16bits(pv * (dm * dpt[r] - dlt_c) * scale);  // -> dK
       }
-      p_x[wave][kvrow_loc][ln] = fa_bf16bits(pv * dm);  // dropped P -> dV
-      ds_x[wave][kvrow_loc][ln] =
-          fa_bf16bits(pv * (dm * dpt[r] - dlt_c) * scale);  // dSt -> dK
+      const int xo = dkv_xoff(ln, 2 * g + hi);
+      *reinterpret_cast<long*>(p_x[wave] + xo) =
+          *reinterpret_cast<const long*>(pk);
+      *reinterpret_cast<long*>(ds_x[wave] + xo) =
+          *reinterpret_cast<const long*>(dk4);
     }
-    __builtin_amdgcn_s_waitcnt(0);
+    v3_wait_lds();
 
-    // dV += Pt dO : A = Pt [32kv x 16q-chunk] own-row, B = dO^T
+    // dV += Pt dO : A = Pt [32kv x 16q-chunk], B = dO, both transposed
 #pragma unroll
     for (int c2 = 0; c2 < 2; ++c2) {
-      bf16x8 pa = *reinterpret_cast<const bf16x8*>(
-          &p_x[wave][ln][c2 * 16 + hi * 8]);
+      bf16x8 pa = v3_tr_frag(p_x[wave] + c2 * 16 * 64 + x_tr[0],
+                             p_x[wave] + c2 * 16 * 64 + x_tr[1]);
+      const char* drows = do_raw + c2 * 16 * SWB;
 #pragma unroll
       for (int t = 0; t < NTO; ++t) {
-        const int dcol = t * 32 + ln;
-        bf16x8 bfrag = *reinterpret_cast<const bf16x8*>(
-            &dot_lds[dcol][(c2 * 16 + hi * 8) ^ (dcol & 0x18)]);
+        bf16x8 bfrag = v3_tr_bfrag<SWB>(drows, qd_tr, t);
         dv_acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
             pa, bfrag, dv_acc[t], 0, 0, 0);
       }
@@ -1712,13 +1857,12 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
     // dK += dSt Q (dSt already exchanged above)
 #pragma unroll
     for (int c2 = 0; c2 < 2; ++c2) {
-      bf16x8 pa = *reinterpret_cast<const bf16x8*>(
-          &ds_x[wave][ln][c2 * 16 + hi * 8]);
+      bf16x8 pa = v3_tr_frag(ds_x[wave] + c2 * 16 * 64 + x_tr[0],
+                             ds_x[wave] + c2 * 16 * 64 + x_tr[1]);
+      const char* qrows = q_raw + c2 * 16 * SWB;
 #pragma unroll
       for (int t = 0; t < NTO; ++t) {
-        const int dcol = t * 32 + ln;
-        bf16x8 bfrag = *reinterpret_cast<const bf16x8*>(
-            &qt_lds[dcol][(c2 * 16 + hi * 8) ^ (dcol & 0x18)]);
+        bf16x8 bfrag = v3_tr_bfrag<SWB>(qrows, qd_tr, t);
         dk_acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
             pa, bfrag, dk_acc[t], 0, 0, 0);
       }
