@@ -373,13 +373,28 @@ class ParallelTransformerLayer(nn.Module):
             return F_ops.bias_dropout_add(total, bias, x,
                                           self.hidden_dropout,
                                           self.training)
-        residual = x
-        h = self.input_norm(x)
+        # fused form: each norm also carries the residual stream, so the
+        # attention add (forward) and both residual-gradient adds (backward)
+        # happen inside the norm kernels
+        fused = (isinstance(self.input_norm, RMSNorm)
+                 and isinstance(self.post_attention_norm, RMSNorm)
+                 and (self.hidden_dropout == 0.0 or not self.training))
+        if fused:
+            residual, h = F_ops.residual_rms_norm(
+                x, None, self.input_norm.weight, self.input_norm.eps)
+        else:
+            residual = x
+            h = self.input_norm(x)
         attn_out = self.attention(h, attention_mask=attention_mask, cache=cache)
-        x = F_ops.bias_dropout_add(attn_out, None, residual,
-                                   self.hidden_dropout, self.training)
+        if fused and torch.is_tensor(attn_out):
+            x, h = F_ops.residual_rms_norm(
+                residual, attn_out, self.post_attention_norm.weight,
+                self.post_attention_norm.eps)
+        else:
+            x = F_ops.bias_dropout_add(attn_out, None, residual,
+                                       self.hidden_dropout, self.training)
+            h = self.post_attention_norm(x)
         residual = x
-        h = self.post_attention_norm(x)
         mlp_out = self.mlp(h)
         x = F_ops.bias_dropout_add(mlp_out, None, residual,
                                    self.hidden_dropout, self.training)

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <c10/hip/HIPStream.h>
 
+#include <string>
 #include <vector>
 
 enum FsDtype { FS_F32 = 0, FS_BF16 = 1, FS_F16 = 2 };
@@ -86,6 +87,13 @@ void fs_flash_attn_bwd_v3_strided(const void*, const void*, const void*,
                                   float, unsigned long long, hipStream_t);
 void fs_rope_inplace(void*, void*, const float*, const float*, int, int, int,
                      int, long, long, long, int, int, int, hipStream_t);
+int fs_fused_norm_vectors(int);
+int fs_fused_norm_bwd_grid(int, int);
+void fs_res_rms_norm_fwd(const void*, const void*, const void*, void*, void*,
+                         float*, int, int, float, int, hipStream_t);
+void fs_res_rms_norm_bwd(const void*, const void*, const void*, const void*,
+                         const float*, void*, float*, void*, int, int, int,
+                         hipStream_t);
 }
 
 // ---------------------------------------------------------------------------
@@ -114,6 +122,75 @@ static std::vector<at::Tensor> rms_norm_bwd(at::Tensor gy, at::Tensor x,
                   gw32.data_ptr<float>(), (int)rows, H, fs_dtype(x),
                   cur_stream());
   return {gx, gw32.to(w.scalar_type())};
+}
+
+// Dispatch branch of the residual RMSNorm entry points for hidden size H:
+// "reg<vectors per thread>" for the register-resident kernels, "lds" for the
+// fallback.
+static std::string fused_norm_branch(int64_t H) {
+  const int nv = fs_fused_norm_vectors((int)H);
+  return nv ? "reg" + std::to_string(nv) : std::string("lds");
+}
+
+// (sum, h, invrms); sum = x + delta rounded to x's dtype, or x itself when
+// delta is absent.  h is the RMSNorm of the rounded sum.
+static std::vector<at::Tensor> residual_rms_norm_fwd(
+    at::Tensor x, c10::optional<at::Tensor> delta, at::Tensor w, double eps) {
+  TORCH_CHECK(x.is_contiguous() && w.is_contiguous());
+  const int H = x.size(-1);
+  TORCH_CHECK(H % 8 == 0, "hidden must be divisible by 8");
+  TORCH_CHECK(w.numel() == H && w.scalar_type() == x.scalar_type());
+  const bool has_delta = delta.has_value();
+  if (has_delta)
+    TORCH_CHECK(delta->is_contiguous() && delta->sizes() == x.sizes() &&
+                delta->scalar_type() == x.scalar_type());
+  if (fs_fused_norm_vectors(H) == 0) {
+    at::Tensor sum = has_delta ? at::add(x, *delta) : x;
+    auto r = rms_norm_fwd(sum, w, eps);
+    return {sum, r[0], r[1]};
+  }
+  const long rows = x.numel() / H;
+  at::Tensor sum = has_delta ? at::empty_like(x) : x;
+  auto h = at::empty_like(x);
+  auto invrms = at::empty({rows}, x.options().dtype(at::kFloat));
+  fs_res_rms_norm_fwd(x.data_ptr(), has_delta ? delta->data_ptr() : nullptr,
+                      w.data_ptr(), has_delta ? sum.data_ptr() : nullptr,
+                      h.data_ptr(), invrms.data_ptr<float>(), (int)rows, H,
+                      (float)eps, fs_dtype(x), cur_stream());
+  return {sum, h, invrms};
+}
+
+// (g, gw); g = norm input gradient (+ g_res when given), gw in w's dtype.
+static std::vector<at::Tensor> residual_rms_norm_bwd(
+    at::Tensor g_h, c10::optional<at::Tensor> g_res, at::Tensor x,
+    at::Tensor w, at::Tensor invrms) {
+  TORCH_CHECK(g_h.is_contiguous() && x.is_contiguous() && w.is_contiguous());
+  TORCH_CHECK(g_h.sizes() == x.sizes() &&
+              g_h.scalar_type() == x.scalar_type());
+  const int H = x.size(-1);
+  const long rows = x.numel() / H;
+  TORCH_CHECK(H % 8 == 0, "hidden must be divisible by 8");
+  TORCH_CHECK(invrms.is_contiguous() && invrms.scalar_type() == at::kFloat &&
+              invrms.numel() == rows, "invrms must be ", rows, " floats");
+  TORCH_CHECK(w.numel() == H);
+  const bool has_res = g_res.has_value();
+  if (has_res)
+    TORCH_CHECK(g_res->is_contiguous() && g_res->sizes() == x.sizes() &&
+                g_res->scalar_type() == x.scalar_type());
+  if (fs_fused_norm_vectors(H) == 0) {
+    auto r = rms_norm_bwd(g_h, x, w, invrms);
+    return {has_res ? at::add(r[0], *g_res) : r[0], r[1]};
+  }
+  TORCH_CHECK(w.scalar_type() == x.scalar_type());
+  auto g = at::empty_like(x);
+  auto gw = at::empty_like(w);
+  auto part = at::empty({fs_fused_norm_bwd_grid((int)rows, H), H},
+                        x.options().dtype(at::kFloat));
+  fs_res_rms_norm_bwd(g_h.data_ptr(), has_res ? g_res->data_ptr() : nullptr,
+                      x.data_ptr(), w.data_ptr(), invrms.data_ptr<float>(),
+                      g.data_ptr(), part.data_ptr<float>(), gw.data_ptr(),
+                      (int)rows, H, fs_dtype(x), cur_stream());
+  return {g, gw};
 }
 
 static std::vector<at::Tensor> layer_norm_fwd(at::Tensor x, at::Tensor w,
@@ -650,6 +727,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("rope_inplace", &rope_inplace);
   mod.def("rms_norm_fwd", &rms_norm_fwd);
   mod.def("rms_norm_bwd", &rms_norm_bwd);
+  mod.def("residual_rms_norm_fwd", &residual_rms_norm_fwd);
+  mod.def("residual_rms_norm_bwd", &residual_rms_norm_bwd);
+  mod.def("fused_norm_branch", &fused_norm_branch);
   mod.def("layer_norm_fwd", &layer_norm_fwd);
   mod.def("layer_norm_bwd", &layer_norm_bwd);
   mod.def("scaled_masked_softmax_fwd", &scaled_masked_softmax_fwd);

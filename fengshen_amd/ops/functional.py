@@ -17,6 +17,7 @@ The eager implementations double as numerics oracles in tests
 from __future__ import annotations
 
 import math
+import os
 from typing import Optional
 
 import torch
@@ -114,12 +115,36 @@ def eager_rms_norm(x: torch.Tensor, weight: torch.Tensor, eps: float):
     return (weight.float() * y).to(x.dtype)
 
 
+def fused_norm_enabled() -> bool:
+    """FENGSHEN_FUSED_NORM=0 forces the LDS-staged norm kernels and the
+    separate residual adds (bias_dropout_add + rms_norm)."""
+    return os.environ.get("FENGSHEN_FUSED_NORM", "1") != "0"
+
+
+def _rms_norm_bwd_eager(g_h, x, weight, invrms):
+    x32 = x.float()
+    g32 = g_h.float()
+    w32 = weight.float()
+    xhat = x32 * invrms
+    gy_w = g32 * w32
+    # d/dx: invrms * (gy_w - xhat * mean(gy_w * xhat))
+    mean_term = (gy_w * xhat).mean(-1, keepdim=True)
+    gx = (invrms * (gy_w - xhat * mean_term)).to(x.dtype)
+    gw = (g32 * xhat).sum(dim=tuple(range(x.dim() - 1))).to(weight.dtype)
+    return gx, gw
+
+
 class _RMSNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, eps):
+        ctx.fused = fused_norm_enabled()
         if use_hip(x):
             x = x.contiguous()  # kernel reads rows as flat vectors
-            out, invrms = get_ext().rms_norm_fwd(x, weight, eps)
+            if ctx.fused:
+                _, out, invrms = get_ext().residual_rms_norm_fwd(
+                    x, None, weight, eps)
+            else:
+                out, invrms = get_ext().rms_norm_fwd(x, weight, eps)
         else:
             x32 = x.float()
             var = x32.pow(2).mean(-1, keepdim=True)
@@ -132,23 +157,74 @@ class _RMSNorm(torch.autograd.Function):
     def backward(ctx, grad_out):
         x, weight, invrms = ctx.saved_tensors
         if use_hip(x):
-            gx, gw = get_ext().rms_norm_bwd(grad_out.contiguous(), x, weight,
-                                            invrms)
+            if ctx.fused:
+                gx, gw = get_ext().residual_rms_norm_bwd(
+                    grad_out.contiguous(), None, x, weight, invrms)
+            else:
+                gx, gw = get_ext().rms_norm_bwd(grad_out.contiguous(), x,
+                                                weight, invrms)
             return gx, gw, None
-        x32 = x.float()
-        g32 = grad_out.float()
-        w32 = weight.float()
-        xhat = x32 * invrms
-        gy_w = g32 * w32
-        # d/dx: invrms * (gy_w - xhat * mean(gy_w * xhat))
-        mean_term = (gy_w * xhat).mean(-1, keepdim=True)
-        gx = (invrms * (gy_w - xhat * mean_term)).to(x.dtype)
-        gw = (g32 * xhat).sum(dim=tuple(range(x.dim() - 1))).to(weight.dtype)
+        gx, gw = _rms_norm_bwd_eager(grad_out, x, weight, invrms)
         return gx, gw, None
 
 
 def rms_norm(x, weight, eps: float = 1e-6):
     return _RMSNorm.apply(x, weight, eps)
+
+
+class _ResidualRMSNorm(torch.autograd.Function):
+    """(res, h) = (x + delta, rms_norm(x + delta)) in one pass; the backward
+    folds the gradient arriving at ``res`` into the norm's input gradient.
+
+    ``res`` is rounded to x's dtype before it is normalised, so both outputs
+    equal a torch add followed by rms_norm; with delta=None ``res`` is x.
+    The backward rounds the norm's input gradient to x's dtype before adding
+    g_res, as the separate add did."""
+
+    @staticmethod
+    def forward(ctx, x, delta, weight, eps):
+        ctx.set_materialize_grads(False)
+        ctx.has_delta = delta is not None
+        if use_hip(x):
+            xc = x.contiguous()  # kernel reads rows as flat vectors
+            dc = delta.contiguous() if ctx.has_delta else None
+            res, h, invrms = get_ext().residual_rms_norm_fwd(
+                xc, dc, weight, eps)
+            if not ctx.has_delta:
+                res = x
+        else:
+            res = x + delta if ctx.has_delta else x
+            r32 = res.float()
+            invrms = torch.rsqrt(r32.pow(2).mean(-1, keepdim=True) + eps)
+            h = (r32 * invrms * weight.float()).to(x.dtype)
+        ctx.save_for_backward(res, weight, invrms)
+        return res, h
+
+    @staticmethod
+    def backward(ctx, g_res, g_h):
+        res, weight, invrms = ctx.saved_tensors
+        if g_h is None:
+            g, gw = g_res, None
+        elif use_hip(res):
+            g, gw = get_ext().residual_rms_norm_bwd(
+                g_h.contiguous(), None if g_res is None else g_res.contiguous(),
+                res.contiguous(), weight, invrms)
+        else:
+            g, gw = _rms_norm_bwd_eager(g_h, res, weight, invrms)
+            if g_res is not None:
+                g = g + g_res
+        return g, (g if ctx.has_delta else None), gw, None
+
+
+def residual_rms_norm(x, delta, weight, eps: float = 1e-6):
+    """-> (res, h): res = x + delta (x itself when delta is None) and
+    h = rms_norm(res).  FENGSHEN_FUSED_NORM=0 composes the same result from
+    bias_dropout_add and rms_norm."""
+    if not fused_norm_enabled():
+        res = x if delta is None else bias_dropout_add(delta, None, x, 0.0,
+                                                       False)
+        return res, rms_norm(res, weight, eps)
+    return _ResidualRMSNorm.apply(x, delta, weight, eps)
 
 
 def eager_layer_norm(x, weight, bias, eps):
