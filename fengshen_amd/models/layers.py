@@ -140,10 +140,13 @@ class ParallelAttention(nn.Module):
                  attention_dropout: float = 0.0, hidden_dropout: float = 0.0,
                  bias: bool = True, init_method=None, output_init_method=None,
                  dtype=None, num_kv_heads: Optional[int] = None,
-                 layer_idx: int = 0, reduce_output: bool = True):
+                 layer_idx: int = 0, reduce_output: bool = True,
+                 attention_type: str = "global",
+                 sparsity_config: Optional[dict] = None):
         super().__init__()
         self.layer_idx = layer_idx
         self.reduce_output = reduce_output
+        self.attention_type = attention_type
         tp = groups.get_tensor_model_parallel_world_size()
         self.hidden_size = hidden_size
         self.num_heads = num_heads
@@ -175,6 +178,67 @@ class ParallelAttention(nn.Module):
             self.max_positions = max_positions
             self._rope_cache = None
 
+        # block-sparse layer (ref transformer.py:246-262: a non-global
+        # attention type swaps in SparseSelfAttention); the layouts are
+        # built for this rank's heads
+        self.sparse_attn = None
+        if attention_type != "global":
+            if not causal:
+                raise ValueError(
+                    f"attention_type {attention_type!r} builds unidirectional "
+                    "layouts and needs causal=True")
+            if attention_dropout > 0:
+                raise ValueError(
+                    f"attention_type {attention_type!r} does not support "
+                    f"attention_dropout ({attention_dropout})")
+            from types import SimpleNamespace
+
+            from fengshen_amd.ops.sparse_attention import (
+                configure_sparse_attention)
+            self.sparse_attn = configure_sparse_attention(
+                SimpleNamespace(sparsity_config=sparsity_config,
+                                max_position_embeddings=max_positions),
+                attention_type, self.num_heads_per_partition)
+
+    @staticmethod
+    def _sparse_keep_mask(attention_mask, b: int, sq: int):
+        """Key-padding mask ([b,1,1,s] or [b,s], True = masked) -> [b, s]
+        keep mask (1 = keep) for SparseSelfAttention."""
+        if attention_mask is None:
+            return None
+        m = attention_mask
+        if m.dim() == 4 and tuple(m.shape) == (b, 1, 1, sq):
+            m = m[:, 0, 0, :]
+        elif not (m.dim() == 2 and tuple(m.shape) == (b, sq)):
+            raise ValueError(
+                "sparse attention takes a key-padding mask of shape "
+                f"[b,1,1,s] or [b,s]; got {tuple(attention_mask.shape)}")
+        return (~m.bool()).to(torch.uint8)
+
+    def _sparse_forward(self, qkv, attention_mask, cache):
+        if cache is not None:
+            raise ValueError(
+                f"attention_type {self.attention_type!r} does not support a "
+                "KV cache")
+        b, sq, _ = qkv.shape
+        np_ = self.num_heads_per_partition
+        hn = self.head_dim
+        keep = self._sparse_keep_mask(attention_mask, b, sq)
+        q, k, v = qkv.chunk(3, dim=-1)
+        q = q.view(b, sq, np_, hn).transpose(1, 2)
+        k = k.view(b, sq, np_, hn).transpose(1, 2)
+        v = v.view(b, sq, np_, hn).transpose(1, 2)
+        if self.rotary:
+            cos, sin = self._rope_tables(q.device, sq)
+            q, k = F_ops.apply_rotary(q, k, cos, sin, offset=0)
+        ctx = self.sparse_attn(q.contiguous(), k.contiguous(), v.contiguous(),
+                               attention_mask=keep, scale=self.norm_factor)
+        ctx = ctx.transpose(1, 2).reshape(b, sq, np_ * hn)
+        out = self.out_proj(ctx)
+        if isinstance(out, tuple) and self.reduce_output:
+            out = out[0]
+        return out
+
     def _rope_tables(self, device, seq_needed: int):
         cache = self._rope_cache
         if (cache is None or cache[0].device != device
@@ -196,6 +260,9 @@ class ParallelAttention(nn.Module):
         hn = self.head_dim
 
         qkv = self.qkv_proj(x)  # [b, sq, 3h/tp]
+
+        if self.sparse_attn is not None:
+            return self._sparse_forward(qkv, attention_mask, cache)
 
         # packed path: rotary in place + strided flash kernels on the
         # projection output itself — no chunk/transpose/contiguous copies
@@ -324,7 +391,9 @@ class ParallelTransformerLayer(nn.Module):
                  attention_dropout: float = 0.0, hidden_dropout: float = 0.0,
                  bias: bool = True, init_method=None, output_init_method=None,
                  dtype=None, layer_idx: int = 0,
-                 parallel_residual: bool = False):
+                 parallel_residual: bool = False,
+                 attention_type: str = "global",
+                 sparsity_config: Optional[dict] = None):
         super().__init__()
         # parallel_residual: GPT-J composition x + attn(ln1 x) + mlp(ln2 x)
         # with ONE deferred TP all-reduce over the summed partials
@@ -337,7 +406,8 @@ class ParallelTransformerLayer(nn.Module):
             attention_dropout=attention_dropout, hidden_dropout=hidden_dropout,
             bias=bias, init_method=init_method,
             output_init_method=output_init_method, dtype=dtype,
-            layer_idx=layer_idx, reduce_output=not parallel_residual)
+            layer_idx=layer_idx, reduce_output=not parallel_residual,
+            attention_type=attention_type, sparsity_config=sparsity_config)
         self.post_attention_norm = get_norm(norm, hidden_size, norm_eps, dtype)
         if mlp_type == "swiglu":
             self.mlp = LLaMAParallelMLP(
@@ -518,11 +588,13 @@ class GMLPBlock(nn.Module):
 def expand_attention_types(attention_config, num_layers: int):
     """Expand a [[types, repeat], ...] spec into a per-layer type list
     (ref models/llama/modeling_llama.py:37-64 semantics): each entry
-    contributes `repeat` layers cycling through its `types`; "all" in a
-    spec means the same types tile the whole depth.
+    contributes its `types` pattern `repeat` times; "all" in a spec means
+    the same types tile the whole depth.
 
     >>> expand_attention_types([[["global"], 2], [["sparse_fixed"], 2]], 4)
     ['global', 'global', 'sparse_fixed', 'sparse_fixed']
+    >>> expand_attention_types([[["global", "bigbird"], 1]], 2)
+    ['global', 'bigbird']
     """
     if attention_config is None:
         return ["global"] * num_layers
@@ -532,8 +604,8 @@ def expand_attention_types(attention_config, num_layers: int):
             for i in range(num_layers):
                 out.append(types[i % len(types)])
             break
-        for i in range(int(repeat)):
-            out.append(types[i % len(types)])
+        for _ in range(int(repeat)):
+            out.extend(types)
     assert len(out) >= num_layers, (
         f"attention_config covers {len(out)} layers, model has {num_layers}")
     return out[:num_layers]

@@ -29,7 +29,14 @@ class LlamaConfig(PretrainedConfig):
                  tie_word_embeddings: bool = False,
                  parallel_residual: bool = False,
                  torch_dtype="bfloat16",
+                 attention_config=None,
+                 sparsity_config=None,
                  **kwargs):
+        # per-layer attention types, [[types, repeat], ...] as taken by
+        # layers.expand_attention_types (None = all "global"), and the
+        # sparsity_config dict of ops.sparse_attention
+        self.attention_config = attention_config
+        self.sparsity_config = sparsity_config
         # GPT-J composition with one deferred TP all-reduce per layer
         self.parallel_residual = parallel_residual
         self.vocab_size = vocab_size

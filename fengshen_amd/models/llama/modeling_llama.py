@@ -27,6 +27,7 @@ from transformers.modeling_outputs import (
 from fengshen_amd.models.layers import (
     ParallelTransformerLayer,
     RMSNorm,
+    expand_attention_types,
     init_normal,
     scaled_init_normal,
 )
@@ -56,6 +57,9 @@ class LlamaModel(LlamaPreTrainedModel):
         om = scaled_init_normal(config.initializer_range, config.num_hidden_layers)
         self.embed_tokens = VocabParallelEmbedding(
             config.vocab_size, config.hidden_size, init_method=im)
+        attn_types = expand_attention_types(
+            getattr(config, "attention_config", None),
+            config.num_hidden_layers)
         self.layers = nn.ModuleList([
             ParallelTransformerLayer(
                 config.hidden_size, config.num_attention_heads, causal=True,
@@ -68,7 +72,9 @@ class LlamaModel(LlamaPreTrainedModel):
                 bias=False, init_method=im, output_init_method=om,
                 layer_idx=i,
                 parallel_residual=getattr(config, "parallel_residual",
-                                          False))
+                                          False),
+                attention_type=attn_types[i],
+                sparsity_config=getattr(config, "sparsity_config", None))
             for i in range(config.num_hidden_layers)])
         self.norm = RMSNorm(config.hidden_size, eps=config.rms_norm_epsilon)
         self.gradient_checkpointing = False

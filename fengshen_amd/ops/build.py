@@ -22,7 +22,8 @@ _TARGET = os.path.join(_OPS_DIR, "_C.so")
 def sources():
     srcs = [os.path.join(_CSRC, "bindings.cpp"),
             os.path.join(_CSRC, "kernels.hip"),
-            os.path.join(_CSRC, "fused_norm.hip")]
+            os.path.join(_CSRC, "fused_norm.hip"),
+            os.path.join(_CSRC, "sparse_flash.hip")]
     fa = os.path.join(_CSRC, "flash_attn.hip")
     if os.path.exists(fa):
         srcs.append(fa)

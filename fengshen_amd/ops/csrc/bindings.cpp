@@ -94,6 +94,16 @@ void fs_res_rms_norm_fwd(const void*, const void*, const void*, void*, void*,
 void fs_res_rms_norm_bwd(const void*, const void*, const void*, const void*,
                          const float*, void*, float*, void*, int, int, int,
                          hipStream_t);
+void fs_sparse_flash_fwd(const void*, const void*, const void*, void*, float*,
+                         const int*, const int*, const int*,
+                         const unsigned char*, int, int, int, int, int, int,
+                         float, hipStream_t);
+void fs_sparse_flash_bwd(const void*, const void*, const void*, const void*,
+                         const void*, const float*, void*, void*, void*,
+                         float*, const int*, const int*, const int*,
+                         const int*, const int*, const int*,
+                         const unsigned char*, int, int, int, int, int, int,
+                         float, hipStream_t);
 }
 
 // ---------------------------------------------------------------------------
@@ -640,7 +650,150 @@ static std::vector<at::Tensor> add_rms_norm(at::Tensor a, at::Tensor b,
   return {sum_out, y};
 }
 
+// --- block-sparse flash attention ------------------------------------------
+// q/k/v [b, h, s, d] bf16 contiguous, d in {64, 96, 128}, s % 16 == 0.
+// Tile lists (ops/sparse_flash.py): CSR over (list head, tile) with LH = h
+// or 1 (one layout shared by all heads); int32, on q's device.
+//   row lists: ptr[LH * ceil(s/128) + 1], idx = 64-key tile index
+//   col lists: ptr[LH * ceil(s/64) + 1],  idx = 128-row query tile index
+// Everything is checked here, on the host, before anything is launched.
+// check_indices additionally copies ptr/idx to the host and verifies the
+// CSR structure and every tile index; lists from build_tile_lists are
+// verified once when they are built, so the autograd path passes false.
+static int check_tile_list(const at::Tensor& ptr, const at::Tensor& idx,
+                           const at::Tensor& mask, const at::Tensor& q,
+                           int h, int n_lists_per_head, int n_idx_tiles,
+                           bool check_indices, const char* name) {
+  for (const at::Tensor* t : {&ptr, &idx, &mask}) {
+    TORCH_CHECK(t->scalar_type() == at::kInt, "sparse_flash: ", name,
+                " lists must be int32");
+    TORCH_CHECK(t->device() == q.device(), "sparse_flash: ", name,
+                " lists must be on the device of q");
+    TORCH_CHECK(t->dim() == 1 && t->is_contiguous(), "sparse_flash: ", name,
+                " lists must be 1-D contiguous");
+  }
+  const int64_t n = ptr.numel() - 1;
+  TORCH_CHECK(n == n_lists_per_head || n == (int64_t)h * n_lists_per_head,
+              "sparse_flash: ", name, "_ptr has ", ptr.numel(),
+              " entries, expected ", n_lists_per_head, "+1 or ",
+              (int64_t)h * n_lists_per_head, "+1");
+  TORCH_CHECK(idx.numel() == mask.numel(), "sparse_flash: ", name,
+              "_idx and ", name, "_mask differ in length");
+  if (check_indices) {
+    auto p = ptr.cpu();
+    auto ix = idx.cpu();
+    const int* pp = p.data_ptr<int>();
+    const int* ip = ix.data_ptr<int>();
+    TORCH_CHECK(pp[0] == 0 && pp[n] == idx.numel(), "sparse_flash: ", name,
+                "_ptr does not span ", name, "_idx");
+    for (int64_t i = 0; i < n; ++i)
+      TORCH_CHECK(pp[i] <= pp[i + 1], "sparse_flash: ", name,
+                  "_ptr is not monotone");
+    for (int64_t i = 0; i < idx.numel(); ++i)
+      TORCH_CHECK(ip[i] >= 0 && ip[i] < n_idx_tiles, "sparse_flash: ", name,
+                  "_idx[", i, "] = ", ip[i], " out of range [0, ",
+                  n_idx_tiles, ")");
+  }
+  return n == n_lists_per_head && h != 1 ? 1 : h;
+}
+
+static void check_sparse_qkv(const at::Tensor& q, const at::Tensor& k,
+                             const at::Tensor& v) {
+  TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda(),
+              "sparse_flash: q/k/v must be on the GPU");
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16 &&
+              k.scalar_type() == at::kBFloat16 &&
+              v.scalar_type() == at::kBFloat16, "sparse_flash: bf16 only");
+  TORCH_CHECK(q.dim() == 4 && k.sizes() == q.sizes() && v.sizes() == q.sizes(),
+              "sparse_flash: q/k/v must be [b, h, s, d] of one shape");
+  TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous(),
+              "sparse_flash: q/k/v must be contiguous");
+  const int64_t d = q.size(3), s = q.size(2);
+  TORCH_CHECK(d == 64 || d == 96 || d == 128,
+              "sparse_flash: head_dim must be 64, 96 or 128");
+  TORCH_CHECK(s >= 16 && s % 16 == 0,
+              "sparse_flash: seq_len must be a positive multiple of 16");
+  TORCH_CHECK(q.size(0) <= 65535 && q.size(1) <= 65535,
+              "sparse_flash: batch and heads are grid dims (<= 65535)");
+}
+
+static const unsigned char* checked_key_mask(
+    const c10::optional<at::Tensor>& km, const at::Tensor& q) {
+  if (!km.has_value()) return nullptr;
+  TORCH_CHECK(km->scalar_type() == at::kByte && km->device() == q.device() &&
+              km->is_contiguous() && km->dim() == 2 &&
+              km->size(0) == q.size(0) && km->size(1) == q.size(2),
+              "sparse_flash: key_mask must be contiguous uint8 [b, s] on the "
+              "device of q");
+  return km->data_ptr<unsigned char>();
+}
+
+static std::vector<at::Tensor> sparse_flash_fwd(
+    at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor row_ptr,
+    at::Tensor row_idx, at::Tensor row_mask,
+    c10::optional<at::Tensor> key_mask, double scale, bool causal,
+    bool check_indices) {
+  check_sparse_qkv(q, k, v);
+  const int b = q.size(0), h = q.size(1), s = q.size(2), d = q.size(3);
+  const int nqt = (s + 127) / 128, nkt = (s + 63) / 64;
+  const int lh = check_tile_list(row_ptr, row_idx, row_mask, q, h, nqt, nkt,
+                                 check_indices, "row");
+  const unsigned char* kmp = checked_key_mask(key_mask, q);
+  auto o = at::empty_like(q);
+  auto lse = at::empty({b, h, s}, q.options().dtype(at::kFloat));
+  fs_sparse_flash_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                      lse.data_ptr<float>(), row_ptr.data_ptr<int>(),
+                      row_idx.data_ptr<int>(), row_mask.data_ptr<int>(), kmp,
+                      b, h, s, d, lh, causal ? 1 : 0, (float)scale,
+                      cur_stream());
+  return {o, lse};
+}
+
+static std::vector<at::Tensor> sparse_flash_bwd(
+    at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor dout,
+    at::Tensor lse, at::Tensor row_ptr, at::Tensor row_idx,
+    at::Tensor row_mask, at::Tensor col_ptr, at::Tensor col_idx,
+    at::Tensor col_mask, c10::optional<at::Tensor> key_mask, double scale,
+    bool causal, bool check_indices) {
+  check_sparse_qkv(q, k, v);
+  const int b = q.size(0), h = q.size(1), s = q.size(2), d = q.size(3);
+  const int nqt = (s + 127) / 128, nkt = (s + 63) / 64;
+  TORCH_CHECK(o.sizes() == q.sizes() && o.is_contiguous() &&
+              o.scalar_type() == at::kBFloat16 && o.device() == q.device(),
+              "sparse_flash_bwd: o must match q");
+  TORCH_CHECK(dout.sizes() == q.sizes() &&
+              dout.scalar_type() == at::kBFloat16 &&
+              dout.device() == q.device(),
+              "sparse_flash_bwd: dout must match q");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+              lse.numel() == (int64_t)b * h * s && lse.device() == q.device(),
+              "sparse_flash_bwd: lse must be fp32 [b, h, s]");
+  const int lh = check_tile_list(row_ptr, row_idx, row_mask, q, h, nqt, nkt,
+                                 check_indices, "row");
+  const int lhc = check_tile_list(col_ptr, col_idx, col_mask, q, h, nkt, nqt,
+                                  check_indices, "col");
+  TORCH_CHECK(lh == lhc, "sparse_flash_bwd: row and column lists disagree on "
+              "per-head vs shared layout");
+  const unsigned char* kmp = checked_key_mask(key_mask, q);
+  auto dout_c = dout.contiguous();
+  auto dq = at::empty_like(q);
+  auto dk = at::empty_like(k);
+  auto dv = at::empty_like(v);
+  auto delta = at::empty({b, h, s}, q.options().dtype(at::kFloat));
+  fs_sparse_flash_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                      dout_c.data_ptr(), lse.data_ptr<float>(), dq.data_ptr(),
+                      dk.data_ptr(), dv.data_ptr(), delta.data_ptr<float>(),
+                      row_ptr.data_ptr<int>(), row_idx.data_ptr<int>(),
+                      row_mask.data_ptr<int>(), col_ptr.data_ptr<int>(),
+                      col_idx.data_ptr<int>(), col_mask.data_ptr<int>(), kmp,
+                      b, h, s, d, lh, causal ? 1 : 0, (float)scale,
+                      cur_stream());
+  return {dq, dk, dv};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
+  mod.def("sparse_flash_fwd", &sparse_flash_fwd);
+  mod.def("sparse_flash_bwd", &sparse_flash_bwd);
   mod.def("w8_gemv", &w8_gemv);
   mod.def("bf16_gemv", &bf16_gemv);
   mod.def("decode_attn", &decode_attn);

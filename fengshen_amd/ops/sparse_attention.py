@@ -4,17 +4,25 @@ Behavioral parity: reference models/megatron/layers/utils.py:187-296
 (configure_sparse_attention) — the reference builds DeepSpeed/Triton
 SparseSelfAttention with one of five sparsity configs (fixed, variable,
 local sliding-window, bigbird, bslongformer).  Here the layouts are
-reproduced exactly as [num_heads, nb, nb] block masks and attention is
-computed blockwise: for every query block only its active key blocks are
-gathered and attended, so memory is O(s * active_blocks * block) instead
-of O(s^2).  The blockwise math runs on whatever device the tensors live
-on (MFMA-backed hipBLASLt batched GEMMs on MI355X); a dedicated HIP
-block-sparse flash kernel is the planned round-2 upgrade and slots in
-behind the same module interface.
+reproduced exactly as [num_heads, nb, nb] block masks.
+
+Two paths sit behind SparseSelfAttention:
+
+- kernel path: bf16 on the GPU, head dim 64/96/128, block 16/32/64/128.
+  The layout becomes tile lists (ops/sparse_flash.py) and the block-sparse
+  flash kernels in csrc/sparse_flash.hip walk them: forward and backward
+  touch only active tiles, nothing of size s x s exists, gradients are
+  bit-reproducible.  A query row that sees no key (all its keys masked)
+  returns 0 there.
+- eager blockwise path: everything else (fp32, CPU, other head dims,
+  block 8), and any input when FENGSHEN_SPARSE_FLASH=0.  For every query
+  block only its active key blocks are gathered and attended, so memory is
+  O(s * active_blocks * block) instead of O(s^2).
 """
 from __future__ import annotations
 
 import math
+import os
 from typing import List, Optional
 
 import torch
@@ -251,6 +259,10 @@ class SparseSelfAttention(nn.Module):
     blocks across heads is gathered; inactive (head, block) pairs are
     masked with -inf before the softmax, intra-diagonal-block causality
     is enforced by index comparison.  Layouts are cached per seq_len.
+
+    bf16 GPU inputs with a supported head dim and block run the
+    block-sparse flash kernels instead (see the module docstring); their
+    tile lists are cached per (seq_len, device) next to the layouts.
     """
 
     def __init__(self, sparsity_config: SparsityConfig,
@@ -260,12 +272,35 @@ class SparseSelfAttention(nn.Module):
         self.max_seq_length = max_seq_length
         self.attn_mask_mode = attn_mask_mode
         self._layouts = {}
+        self._tile_lists = {}
 
     def layout(self, seq_len: int, device) -> torch.Tensor:
         key = (seq_len, str(device))
         if key not in self._layouts:
             self._layouts[key] = self.config.make_layout(seq_len).to(device)
         return self._layouts[key]
+
+    def tile_lists(self, seq_len: int, device):
+        """Tile lists of the layout for the block-sparse flash kernels."""
+        key = (seq_len, str(device))
+        if key not in self._tile_lists:
+            from fengshen_amd.ops.sparse_flash import build_tile_lists
+            lists = build_tile_lists(self.config.make_layout(seq_len),
+                                     self.config.block, seq_len)
+            self._tile_lists[key] = lists.to(device)
+        return self._tile_lists[key]
+
+    def uses_kernel(self, q: torch.Tensor) -> bool:
+        """True if forward(q, ...) takes the block-sparse flash kernels."""
+        if not q.is_cuda or q.dtype != torch.bfloat16:
+            return False
+        if os.environ.get("FENGSHEN_SPARSE_FLASH") == "0":
+            return False
+        from fengshen_amd.ops import sparse_flash as sf
+        from fengshen_amd.ops import use_hip
+        return (q.shape[-1] in sf.SPARSE_FLASH_DIMS
+                and self.config.block in sf.SPARSE_FLASH_BLOCKS
+                and use_hip(q) and sf.sparse_flash_available())
 
     def density(self, seq_len: int) -> float:
         lay = self.config.make_layout(seq_len)
@@ -277,8 +312,14 @@ class SparseSelfAttention(nn.Module):
         B = self.config.block
         nb = s // B
         scale = scale if scale is not None else 1.0 / math.sqrt(hn)
-        layout = self.layout(s, q.device)  # [np, nb, nb]
         causal = self.config.attention == "unidirectional"
+        if self.uses_kernel(q):
+            from fengshen_amd.ops.sparse_flash import block_sparse_attention
+            self.config.num_blocks(s)  # s % block == 0
+            return block_sparse_attention(
+                q, k, v, self.tile_lists(s, q.device), scale, causal,
+                key_mask=attention_mask)
+        layout = self.layout(s, q.device)  # [np, nb, nb]
 
         kb = k.view(b, np_, nb, B, hn)
         vb = v.view(b, np_, nb, B, hn)
