@@ -104,7 +104,9 @@ def main():
         from fengshen_amd.tokenizer import SimpleCharTokenizer as FakeTokenizer
         tokenizer = FakeTokenizer()
 
-    collator = SftCollator(tokenizer, max_seq_length=args.max_seq_length)
+    # lengths in multiples of 64 keep padded batches on the flash kernels
+    collator = SftCollator(tokenizer, max_seq_length=args.max_seq_length,
+                           pad_to_multiple_of=64)
     datasets = None
     if not args.train_file and not args.datasets_name:
         datasets = {"train": synthetic_sft()}

@@ -12,7 +12,7 @@ Behavioral parity:
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Any, Dict, List
+from typing import Any, Dict, List, Optional
 
 import numpy as np
 import torch
@@ -101,6 +101,10 @@ class SftCollator:
     query_key: str = "query"
     answer_key: str = "answer"
     pad_to_max: bool = False
+    # round the padded length up to a multiple of this (64: the tile of the
+    # flash attention kernels, which take padded causal batches only at such
+    # lengths); None pads to the longest sample as before
+    pad_to_multiple_of: Optional[int] = None
 
     def __call__(self, samples: List[Dict]) -> Dict[str, torch.Tensor]:
         input_ids, labels = [], []
@@ -128,6 +132,9 @@ class SftCollator:
             labels.append(lbl)
         L = self.max_seq_length if self.pad_to_max else \
             max(len(x) for x in input_ids)
+        if self.pad_to_multiple_of:
+            m = self.pad_to_multiple_of
+            L = (L + m - 1) // m * m
         pad_id = self.tokenizer.pad_token_id or 0
         attn = [[1] * len(x) + [0] * (L - len(x)) for x in input_ids]
         input_ids = [_pad(x, L, pad_id) for x in input_ids]

@@ -72,7 +72,12 @@ class GPT2Model(GPT2PreTrainedModel):
         self.wte = v
 
     def forward(self, input_ids, attention_mask=None, past_key_values=None,
-                use_cache: bool = False, position_ids=None, **_kw):
+                use_cache: bool = False, position_ids=None, kstart=None,
+                **_kw):
+        """kstart: int32 [b, s] per-row key start of a packed batch
+        (ops.flash.kstart_from_eod), in place of its [b, 1, s, s] mask; a
+        mask of that form or a padded one is converted here, once for all
+        layers."""
         b, s = input_ids.shape
         cache = past_key_values
         if use_cache and cache is None:
@@ -91,6 +96,9 @@ class GPT2Model(GPT2PreTrainedModel):
                 mask = (attention_mask == 0)[:, None, None, :]
         elif attention_mask is not None:
             mask = attention_mask
+        if kstart is None:
+            from fengshen_amd.ops.flash import model_kstart
+            kstart = model_kstart(mask, h)
 
         skip = self.gradient_checkpointing_skip_interval
         for i, layer in enumerate(self.h):
@@ -100,9 +108,11 @@ class GPT2Model(GPT2PreTrainedModel):
                 ckpt = False
             if ckpt:
                 h = activation_checkpoint(
-                    lambda x, m, lyr=layer: lyr(x, attention_mask=m), h, mask)
+                    lambda x, m, ks, lyr=layer: lyr(x, attention_mask=m,
+                                                    kstart=ks),
+                    h, mask, kstart)
             else:
-                h = layer(h, attention_mask=mask, cache=cache)
+                h = layer(h, attention_mask=mask, cache=cache, kstart=kstart)
         h = self.ln_f(h)
         return BaseModelOutputWithPast(last_hidden_state=h, past_key_values=cache)
 
@@ -126,10 +136,12 @@ class GPT2LMHeadModel(GPT2PreTrainedModel, GenerationMixin):
 
     def forward(self, input_ids, attention_mask=None, labels=None,
                 past_key_values=None, use_cache: bool = False,
-                position_ids=None, return_dict: bool = True, **_kw):
+                position_ids=None, return_dict: bool = True, kstart=None,
+                **_kw):
         out = self.transformer(input_ids, attention_mask=attention_mask,
                                past_key_values=past_key_values,
-                               use_cache=use_cache, position_ids=position_ids)
+                               use_cache=use_cache, position_ids=position_ids,
+                               kstart=kstart)
         h = out.last_hidden_state
         logits_parallel = parallel_lm_logits(h, self.transformer.wte.weight,
                                              parallel_output=True)

@@ -252,9 +252,12 @@ class ParallelAttention(nn.Module):
 
     def forward(self, x: torch.Tensor,
                 attention_mask: Optional[torch.Tensor] = None,
-                cache=None):
+                cache=None, kstart: Optional[torch.Tensor] = None):
         """cache: any object with .get_seq_length(layer_idx) and
-        .update(k, v, layer_idx) -> (k_full, v_full) — HF DynamicCache works."""
+        .update(k, v, layer_idx) -> (k_full, v_full) — HF DynamicCache works.
+        kstart: int32 [b, s] per-row key start of a padded or packed causal
+        batch (ops/flash.py), instead of or next to the dense mask it
+        stands for; only without a cache or at an empty one."""
         b, sq, _ = x.shape
         np_ = self.num_heads_per_partition
         hn = self.head_dim
@@ -268,20 +271,26 @@ class ParallelAttention(nn.Module):
         # projection output itself — no chunk/transpose/contiguous copies
         if cache is None and F_ops.use_hip(qkv):
             from fengshen_amd.ops.flash import (
-                mask_to_klens, packed_attn_eligible, packed_self_attention)
+                mask_to_klens, mask_to_kstart, packed_attn_eligible,
+                packed_self_attention, varlen_flash_enabled)
             drop = self.attention_dropout if self.training else 0.0
-            if packed_attn_eligible(qkv, hn, self.causal, attention_mask,
-                                    drop):
-                klens = None
-                if attention_mask is not None:
+            masked = attention_mask is not None or kstart is not None
+            if packed_attn_eligible(qkv, hn, self.causal,
+                                    attention_mask if kstart is None
+                                    else kstart, drop):
+                klens = ks = None
+                if self.causal and masked and varlen_flash_enabled():
+                    ks = kstart if kstart is not None else \
+                        mask_to_kstart(attention_mask, sq)
+                elif not self.causal and attention_mask is not None:
                     klens = mask_to_klens(attention_mask, sq)
-                if attention_mask is None or klens is not None:
+                if not masked or klens is not None or ks is not None:
                     cos = sin = None
                     if self.rotary:
                         cos, sin = self._rope_tables(qkv.device, sq)
                     ctx = packed_self_attention(
                         qkv, np_, cos, sin, 0, self.norm_factor,
-                        causal=self.causal, klens=klens)
+                        causal=self.causal, klens=klens, kstart=ks)
                     out = self.out_proj(ctx)
                     if isinstance(out, tuple) and self.reduce_output:
                         out = out[0]
@@ -307,9 +316,13 @@ class ParallelAttention(nn.Module):
             causal = False  # single-token decode: all past is visible
         # chunked prefill (offset>0, sq>1) stays causal: functional.attention
         # builds the offset-aware rectangular mask (triu(1+sk-sq)).
+        if kstart is not None and offset > 0:
+            raise ValueError("kstart describes a whole sequence: it cannot "
+                             "be combined with a non-empty KV cache")
         ctx = F_ops.attention(q, k, v, causal=causal, mask=attention_mask,
                               dropout_p=self.attention_dropout,
-                              training=self.training, scale=self.norm_factor)
+                              training=self.training, scale=self.norm_factor,
+                              kstart=kstart)
         ctx = ctx.transpose(1, 2).reshape(b, sq, np_ * hn)
         out = self.out_proj(ctx)
         if isinstance(out, tuple) and self.reduce_output:
@@ -427,13 +440,13 @@ class ParallelTransformerLayer(nn.Module):
             return out[0], out[1]
         return out, None
 
-    def forward(self, x, attention_mask=None, cache=None):
+    def forward(self, x, attention_mask=None, cache=None, kstart=None):
         if self.parallel_residual:
             from fengshen_amd.parallel.mappings import (
                 reduce_from_tensor_model_parallel_region)
             ap, ab = self._split_partial(self.attention(
                 self.input_norm(x), attention_mask=attention_mask,
-                cache=cache))
+                cache=cache, kstart=kstart))
             mp, mb = self._split_partial(
                 self.mlp(self.post_attention_norm(x)))
             total = reduce_from_tensor_model_parallel_region(ap + mp)
@@ -455,7 +468,8 @@ class ParallelTransformerLayer(nn.Module):
         else:
             residual = x
             h = self.input_norm(x)
-        attn_out = self.attention(h, attention_mask=attention_mask, cache=cache)
+        attn_out = self.attention(h, attention_mask=attention_mask,
+                                  cache=cache, kstart=kstart)
         if fused and torch.is_tensor(attn_out):
             x, h = F_ops.residual_rms_norm(
                 residual, attn_out, self.post_attention_norm.weight,

@@ -92,7 +92,12 @@ class LlamaModel(LlamaPreTrainedModel):
     def forward(self, input_ids: torch.Tensor,
                 attention_mask: Optional[torch.Tensor] = None,
                 past_key_values=None, use_cache: bool = False,
-                inputs_embeds: Optional[torch.Tensor] = None, **_kw):
+                inputs_embeds: Optional[torch.Tensor] = None,
+                kstart: Optional[torch.Tensor] = None, **_kw):
+        """kstart: int32 [b, s] per-row key start of a packed batch
+        (ops.flash.kstart_from_eod): row i attends to kstart[i] <= j <= i.
+        It replaces the [b, 1, s, s] mask of such a batch; a padded
+        ``attention_mask`` is converted here, once for all layers."""
         h = inputs_embeds if inputs_embeds is not None else \
             self.embed_tokens(input_ids)
         # mask convention: internal "True = masked" [b,1,sq,sk]; HF passes
@@ -110,6 +115,9 @@ class LlamaModel(LlamaPreTrainedModel):
         if use_cache and cache is None:
             from transformers.cache_utils import DynamicCache
             cache = DynamicCache()
+        if kstart is None:
+            from fengshen_amd.ops.flash import model_kstart
+            kstart = model_kstart(mask, h)
 
         skip = self.gradient_checkpointing_skip_interval
         for i, layer in enumerate(self.layers):
@@ -119,9 +127,11 @@ class LlamaModel(LlamaPreTrainedModel):
                 ckpt = False  # selective: keep this layer's activations
             if ckpt:
                 h = activation_checkpoint(
-                    lambda x, m, lyr=layer: lyr(x, attention_mask=m), h, mask)
+                    lambda x, m, ks, lyr=layer: lyr(x, attention_mask=m,
+                                                    kstart=ks),
+                    h, mask, kstart)
             else:
-                h = layer(h, attention_mask=mask, cache=cache)
+                h = layer(h, attention_mask=mask, cache=cache, kstart=kstart)
         h = self.norm(h)
         return BaseModelOutputWithPast(last_hidden_state=h,
                                        past_key_values=cache)
@@ -150,10 +160,11 @@ class LlamaForCausalLM(LlamaPreTrainedModel, GenerationMixin):
                 attention_mask: Optional[torch.Tensor] = None,
                 labels: Optional[torch.Tensor] = None,
                 past_key_values=None, use_cache: bool = False,
-                inputs_embeds=None, return_dict: bool = True, **_kw):
+                inputs_embeds=None, return_dict: bool = True,
+                kstart: Optional[torch.Tensor] = None, **_kw):
         out = self.model(input_ids, attention_mask=attention_mask,
                          past_key_values=past_key_values, use_cache=use_cache,
-                         inputs_embeds=inputs_embeds)
+                         inputs_embeds=inputs_embeds, kstart=kstart)
         h = out.last_hidden_state
         logits_parallel = self.lm_head(h)  # [b, s, V/tp]
 

@@ -85,6 +85,15 @@ void fs_flash_attn_bwd_v3_strided(const void*, const void*, const void*,
                                   const long*, const long*, const long*,
                                   const long*, int, int, int, int, int, float,
                                   float, unsigned long long, hipStream_t);
+void fs_flash_attn_fwd_v3_kstart(const void*, const void*, const void*, void*,
+                                 float*, const int*, const long*, const long*,
+                                 int, int, int, int, float, hipStream_t);
+void fs_flash_attn_bwd_v3_kstart(const void*, const void*, const void*,
+                                 const void*, const void*, const float*,
+                                 void*, void*, void*, float*, const int*,
+                                 const int*, const long*, const long*,
+                                 const long*, const long*, int, int, int, int,
+                                 float, hipStream_t);
 void fs_rope_inplace(void*, void*, const float*, const float*, int, int, int,
                      int, long, long, long, int, int, int, hipStream_t);
 int fs_fused_norm_vectors(int);
@@ -495,10 +504,69 @@ static const int* checked_klens(const c10::optional<at::Tensor>& klens,
   return klens->data_ptr<int>();
 }
 
+// Per-row key start of the causal v3 kernels (ops/flash.py): kstart [b, s]
+// int32, row i sees keys kstart[i] <= j <= i; qend [b, s/64] int32 is the
+// query-loop bound of dkv (backward only).  Dtype, device, layout, shape
+// and the options that exclude kstart are checked here, on the host, before
+// anything is launched.  The kernels clamp what they read, so a bad value
+// cannot move an address; check_values additionally copies both tensors to
+// the host and verifies 0 <= kstart[i] <= i, that kstart is non-decreasing
+// and that qend is the bound that follows from it.
+static void check_kstart(const at::Tensor& kstart,
+                         const c10::optional<at::Tensor>& qend, bool need_qend,
+                         const at::Tensor& q, bool causal, double drop_p,
+                         bool has_klens, bool check_values) {
+  const int64_t b = q.size(0), s = q.size(2);
+  TORCH_CHECK(causal, "flash v3: kstart needs causal=True");
+  TORCH_CHECK(drop_p == 0.0, "flash v3: kstart does not support dropout");
+  TORCH_CHECK(!has_klens, "flash v3: kstart and klens exclude each other");
+  TORCH_CHECK(need_qend == qend.has_value(),
+              need_qend ? "flash v3: backward with kstart needs qend"
+                        : "flash v3: qend is a backward argument");
+  TORCH_CHECK(kstart.scalar_type() == at::kInt, "flash v3: kstart must be int32");
+  TORCH_CHECK(kstart.is_cuda() && kstart.device() == q.device(),
+              "flash v3: kstart must be on the device of q");
+  TORCH_CHECK(kstart.dim() == 2 && kstart.size(0) == b && kstart.size(1) == s,
+              "flash v3: kstart must be [", b, ", ", s, "]");
+  TORCH_CHECK(kstart.is_contiguous(), "flash v3: kstart must be contiguous");
+  if (need_qend) {
+    TORCH_CHECK(qend->scalar_type() == at::kInt, "flash v3: qend must be int32");
+    TORCH_CHECK(qend->is_cuda() && qend->device() == q.device(),
+                "flash v3: qend must be on the device of q");
+    TORCH_CHECK(qend->dim() == 2 && qend->size(0) == b &&
+                    qend->size(1) == s / 64,
+                "flash v3: qend must be [", b, ", ", s / 64, "]");
+    TORCH_CHECK(qend->is_contiguous(), "flash v3: qend must be contiguous");
+  }
+  if (!check_values) return;
+  auto ks = kstart.cpu();
+  const int* kp = ks.data_ptr<int>();
+  for (int64_t bi = 0; bi < b; ++bi)
+    for (int64_t i = 0; i < s; ++i) {
+      const int v = kp[bi * s + i];
+      TORCH_CHECK(v >= 0 && v <= i, "flash v3: kstart[", bi, ", ", i, "] = ",
+                  v, " outside [0, ", i, "]");
+      TORCH_CHECK(i == 0 || v >= kp[bi * s + i - 1], "flash v3: kstart[", bi,
+                  "] decreases at ", i);
+    }
+  if (!need_qend) return;
+  auto qe = qend->cpu();
+  const int* ep = qe.data_ptr<int>();
+  for (int64_t bi = 0; bi < b; ++bi) {
+    int64_t i = 0;
+    for (int64_t t = 0; t < s / 64; ++t) {
+      while (i + 1 < s && kp[bi * s + i + 1] <= 64 * t + 63) ++i;
+      TORCH_CHECK(ep[bi * (s / 64) + t] == i, "flash v3: qend[", bi, ", ", t,
+                  "] = ", ep[bi * (s / 64) + t], ", expected ", i);
+    }
+  }
+}
+
 // Writes o in place; returns lse [b, h, s] fp32.
 static at::Tensor flash_attn_fwd_v3_strided(
     at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, double scale,
-    bool causal, c10::optional<at::Tensor> klens) {
+    bool causal, c10::optional<at::Tensor> klens,
+    c10::optional<at::Tensor> kstart, bool check_values) {
   TORCH_CHECK(q.dim() == 4, "q must be [b, h, s, d]");
   const int b = q.size(0), h = q.size(1), s = q.size(2), d = q.size(3);
   TORCH_CHECK((d == 128 || d == 96 || d == 64) && s % 64 == 0 && s >= 64,
@@ -509,11 +577,21 @@ static at::Tensor flash_attn_fwd_v3_strided(
   check_strided_view(o, "o", b, h, s, d);
   check_same_strides(q, k, "q and k");
   check_same_strides(q, v, "q and v");
+  if (kstart.has_value())
+    check_kstart(*kstart, c10::nullopt, false, q, causal, 0.0,
+                 klens.has_value(), check_values);
   const int* klp = checked_klens(klens, causal, b);
   long qs[3], os[3];
   strides3(q, qs);
   strides3(o, os);
   auto lse = at::empty({b, h, s}, q.options().dtype(at::kFloat));
+  if (kstart.has_value()) {
+    fs_flash_attn_fwd_v3_kstart(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                                o.data_ptr(), lse.data_ptr<float>(),
+                                kstart->data_ptr<int>(), qs, os, b, h, s, d,
+                                (float)scale, cur_stream());
+    return lse;
+  }
   fs_flash_attn_fwd_v3_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                                o.data_ptr(), lse.data_ptr<float>(), klp, qs,
                                os, b, h, s, d, causal ? 1 : 0, (float)scale,
@@ -525,7 +603,9 @@ static at::Tensor flash_attn_fwd_v3_strided(
 static void flash_attn_bwd_v3_strided(
     at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor dout,
     at::Tensor lse, at::Tensor dq, at::Tensor dk, at::Tensor dv, double scale,
-    bool causal, c10::optional<at::Tensor> klens) {
+    bool causal, c10::optional<at::Tensor> klens,
+    c10::optional<at::Tensor> kstart, c10::optional<at::Tensor> qend,
+    bool check_values) {
   TORCH_CHECK(q.dim() == 4, "q must be [b, h, s, d]");
   const int b = q.size(0), h = q.size(1), s = q.size(2), d = q.size(3);
   TORCH_CHECK((d == 128 || d == 96 || d == 64) && s % 64 == 0 && s >= 64,
@@ -545,6 +625,11 @@ static void flash_attn_bwd_v3_strided(
   TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat &&
               lse.is_contiguous() && lse.numel() == (int64_t)b * h * s,
               "lse must be contiguous fp32 [b, h, s]");
+  if (kstart.has_value())
+    check_kstart(*kstart, qend, true, q, causal, 0.0, klens.has_value(),
+                 check_values);
+  else
+    TORCH_CHECK(!qend.has_value(), "flash v3: qend without kstart");
   const int* klp = checked_klens(klens, causal, b);
   long qs[3], os[3], dos[3], gs[3];
   strides3(q, qs);
@@ -552,6 +637,15 @@ static void flash_attn_bwd_v3_strided(
   strides3(dout, dos);
   strides3(dq, gs);
   auto delta = at::empty({b, h, s}, q.options().dtype(at::kFloat));
+  if (kstart.has_value()) {
+    fs_flash_attn_bwd_v3_kstart(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+        dout.data_ptr(), lse.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(),
+        dv.data_ptr(), delta.data_ptr<float>(), kstart->data_ptr<int>(),
+        qend->data_ptr<int>(), qs, os, dos, gs, b, h, s, d, (float)scale,
+        cur_stream());
+    return;
+  }
   fs_flash_attn_bwd_v3_strided(
       q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(),
       lse.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
@@ -834,9 +928,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
                                   at::Tensor o, at::Tensor dout,
                                   at::Tensor lse, double scale, bool causal,
                                   c10::optional<at::Tensor> klens,
-                                  double drop_p, int64_t seed) {
+                                  double drop_p, int64_t seed,
+                                  c10::optional<at::Tensor> kstart,
+                                  c10::optional<at::Tensor> qend,
+                                  bool check_values) {
     const int b = q.size(0), h = q.size(1), s = q.size(2), d = q.size(3);
     TORCH_CHECK((d == 128 || d == 96 || d == 64) && s % 64 == 0);
+    if (kstart.has_value()) {
+      // the kstart kernels have one (strided) entry; contiguous operands
+      // are its special case and get all of its checks
+      TORCH_CHECK(drop_p == 0.0, "flash v3: kstart does not support dropout");
+      TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous());
+      auto dq = at::empty_like(q);
+      auto dk = at::empty_like(k);
+      auto dv = at::empty_like(v);
+      flash_attn_bwd_v3_strided(q, k, v, o, dout.contiguous(), lse, dq, dk,
+                                dv, scale, causal, klens, kstart, qend,
+                                check_values);
+      return std::vector<at::Tensor>{dq, dk, dv};
+    }
+    TORCH_CHECK(!qend.has_value(), "flash v3: qend without kstart");
     const int* klp = nullptr;
     if (klens.has_value()) klp = klens->data_ptr<int>();
     auto dq = at::empty_like(q);
@@ -850,16 +961,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
                          s, d, causal ? 1 : 0, (float)scale, (float)drop_p,
                          (unsigned long long)seed, cur_stream());
     return std::vector<at::Tensor>{dq, dk, dv};
-  });
+  }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("dout"),
+     py::arg("lse"), py::arg("scale"), py::arg("causal"), py::arg("klens"),
+     py::arg("drop_p"), py::arg("seed"), py::arg("kstart") = py::none(),
+     py::arg("qend") = py::none(), py::arg("check_values") = false);
   mod.def("flash_attn_fwd_v3", [](at::Tensor q, at::Tensor k, at::Tensor v,
                                   double scale, bool causal,
                                   c10::optional<at::Tensor> klens,
-                                  double drop_p, int64_t seed) {
+                                  double drop_p, int64_t seed,
+                                  c10::optional<at::Tensor> kstart,
+                                  bool check_values) {
     TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous());
     TORCH_CHECK(q.scalar_type() == at::kBFloat16);
     const int b = q.size(0), h = q.size(1), s = q.size(2), d = q.size(3);
     TORCH_CHECK((d == 128 || d == 96 || d == 64) && s % 64 == 0 && s >= 64);
     TORCH_CHECK(k.size(2) == s, "v3 is self-attention (sq == sk)");
+    if (kstart.has_value()) {
+      TORCH_CHECK(drop_p == 0.0, "flash v3: kstart does not support dropout");
+      auto o = at::empty_like(q);
+      auto lse = flash_attn_fwd_v3_strided(q, k, v, o, scale, causal, klens,
+                                           kstart, check_values);
+      return std::vector<at::Tensor>{o, lse};
+    }
     const int* klp = nullptr;
     if (klens.has_value()) {
       TORCH_CHECK(klens->scalar_type() == at::kInt
@@ -873,10 +996,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
                          d, causal ? 1 : 0, (float)scale, (float)drop_p,
                          (unsigned long long)seed, cur_stream());
     return std::vector<at::Tensor>{o, lse};
-  });
+  }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
+     py::arg("causal"), py::arg("klens"), py::arg("drop_p"), py::arg("seed"),
+     py::arg("kstart") = py::none(), py::arg("check_values") = false);
   mod.def("flash_attn_bwd", &flash_attn_bwd);
-  mod.def("flash_attn_fwd_v3_strided", &flash_attn_fwd_v3_strided);
-  mod.def("flash_attn_bwd_v3_strided", &flash_attn_bwd_v3_strided);
+  mod.def("flash_attn_fwd_v3_strided", &flash_attn_fwd_v3_strided,
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
+          py::arg("scale"), py::arg("causal"), py::arg("klens"),
+          py::arg("kstart") = py::none(), py::arg("check_values") = false);
+  mod.def("flash_attn_bwd_v3_strided", &flash_attn_bwd_v3_strided,
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
+          py::arg("dout"), py::arg("lse"), py::arg("dq"), py::arg("dk"),
+          py::arg("dv"), py::arg("scale"), py::arg("causal"),
+          py::arg("klens"), py::arg("kstart") = py::none(),
+          py::arg("qend") = py::none(), py::arg("check_values") = false);
   mod.def("rope_inplace", &rope_inplace);
   mod.def("rms_norm_fwd", &rms_norm_fwd);
   mod.def("rms_norm_bwd", &rms_norm_bwd);

@@ -1079,6 +1079,36 @@ __device__ __forceinline__ int dkv_xoff(int row, int u) {
   return 64 * row + 8 * (u ^ ((row >> 1) & 7));
 }
 
+// ---- per-row key start (KS instantiations) ---------------------------------
+// kstart [b, s] int32: query row i sees keys kstart[i] <= j <= i, which is
+// right padding (0), left padding by p (p), packed documents (start of the
+// row's document) and pad rows (i) in one mask.  The value is clamped into
+// [0, row] where it is read, so whatever it holds can change which keys a
+// row sees and never an address; every row keeps at least its own key.
+__device__ __forceinline__ int v3_kstart_at(const int* ksb, int row) {
+  return min(max(ksb[row], 0), row);
+}
+
+// Minimum of v over the wave, as a scalar.
+__device__ __forceinline__ int v3_wave_min(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return __builtin_amdgcn_readfirstlane(v);
+}
+
+// Smallest key start of the 256 query rows of block `blk`: no row of the
+// block sees a key before it, so the key loop starts at that key's tile.
+// Every wave computes it for itself (4 loads per lane and one butterfly),
+// which needs neither LDS nor a barrier.
+__device__ __forceinline__ int v3_block_kstart_min(const int* ksb, int blk,
+                                                   int lane, int s) {
+  int m = s;
+#pragma unroll
+  for (int j = 0; j < V3_QBLK / 64; ++j)
+    m = min(m, v3_kstart_at(ksb, min(blk * V3_QBLK + 64 * j + lane, s - 1)));
+  return v3_wave_min(m);
+}
+
 // delta[b,h,s] = rowsum(dO * O) over strided rows; same per-row arithmetic
 // as flash_delta_kernel.  Grid (x, h, b): blockIdx.y/z pick the head and
 // batch, so the [b, h, s] output index needs no division; the 4 waves of a
@@ -1108,7 +1138,7 @@ void flash_delta_v3_kernel(const bf16_t* __restrict__ dO,
   }
 }
 
-template <int D, bool CAUSAL, bool HAS_DROP>
+template <int D, bool CAUSAL, bool HAS_DROP, bool KS = false>
 __global__ __launch_bounds__(FA_WAVES * 64)
 void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
                               const bf16_t* __restrict__ K,
@@ -1119,7 +1149,9 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
                               FaStrides qs, FaStrides os,
                               int b, int h, int s, float scale,
                               unsigned int drop_thresh, float keep_scale,
-                              unsigned long long drop_seed) {
+                              unsigned long long drop_seed,
+                              const int* __restrict__ kstart) {
+  static_assert(!KS || (CAUSAL && !HAS_DROP), "kstart: causal, no dropout");
   constexpr int NC = D / 16;     // MFMA K=16 chunks
   constexpr int NTO = D / 32;    // 32-wide output d-tiles
   constexpr int SWB = fa_swb(D);
@@ -1167,7 +1199,23 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
     q_frag[c] = raw;
   }
 
-  float m_run = -INFINITY, l_run = 0.f;   // per-lane: row my_q
+  // KS: this lane's key start, the wave's smallest one (a tile that ends
+  // before it is invisible to the whole wave) and the block's first tile
+  int ks_q = 0, ks_w = 0, kt0 = 0;
+  if (KS) {
+    const int* ksb = kstart + (long)blockIdx.z * s;
+    ks_q = v3_kstart_at(ksb, my_q);
+    ks_w = v3_wave_min(ks_q);
+    kt0 = v3_block_kstart_min(ksb, blockIdx.x, lane, s) / V3_KVBLK;
+  }
+
+  // per-lane: row my_q.  KS: a wave runs a tile as soon as one of its rows
+  // sees a key in it, so a row can meet tiles in which all of its own keys
+  // are masked before it meets a visible one.  A finite start keeps
+  // m_new - m_run and p - m_new free of inf - inf there (alpha = 1 on
+  // l = 0, then alpha = exp(-1e30 - m) = 0 at the first visible key, the
+  // value the -inf guard below gives the plain kernels).
+  float m_run = KS ? -1e30f : -INFINITY, l_run = 0.f;
   f32x16 o_acc[NTO];
 #pragma unroll
   for (int t = 0; t < NTO; ++t) {
@@ -1193,14 +1241,15 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
   for (int sweep = 0; sweep < SWEEPS; ++sweep) {
     const int i = tid * 8 + sweep * (FA_WAVES * 64 * 8);
     if (i < ELEMS) {
-      const long kr = min(i / D, s - 1);
+      const long kr = KS ? min(kt0 * V3_KVBLK + i / D, s - 1)
+                         : min(i / D, s - 1);
       const int kc = i % D;
       k_reg[sweep] = *reinterpret_cast<const bf16x8*>(Kp + kr * qs.r + kc);
       v_reg[sweep] = *reinterpret_cast<const bf16x8*>(Vp + kr * qs.r + kc);
     }
   }
 
-  // stage tile 0 into buffer 0
+  // stage the first tile into buffer 0
   {
 #pragma unroll
     for (int sweep = 0; sweep < SWEEPS; ++sweep) {
@@ -1225,7 +1274,7 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
   const int q_last_w = __builtin_amdgcn_readfirstlane(q0c) + 31;
 
   int cur = 0;
-  for (int kt = 0; kt < n_kv_tiles; ++kt) {
+  for (int kt = KS ? kt0 : 0; kt < n_kv_tiles; ++kt) {
     const int k_base = kt * V3_KVBLK;
     __syncthreads();  // publishes buf[cur]; everyone done with buf[cur^1]
     if (kt + 1 < n_kv_tiles) {
@@ -1242,7 +1291,8 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
       }
     }
 
-    if (!CAUSAL || k_base <= q_last_w) {
+    if ((!CAUSAL || k_base <= q_last_w) &&
+        (!KS || k_base + V3_KVBLK > ks_w)) {
       // ---- S^T = K_tile @ (sQ)^T : two 32x32 kv-tiles ---------------------
       f32x16 st[2];
 #pragma unroll
@@ -1273,7 +1323,8 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
         for (int r = 0; r < 16; ++r) {
           const int kcol = k_base + nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
           float v = st[nt][r];
-          if (CAUSAL ? (kcol > my_q) : (kcol >= klen)) v = -INFINITY;
+          if (CAUSAL ? (kcol > my_q || (KS && kcol < ks_q)) : (kcol >= klen))
+            v = -INFINITY;
           p[nt * 16 + r] = v;
           tmax = fmaxf(tmax, v);
         }
@@ -1423,7 +1474,7 @@ extern "C" void fs_flash_attn_fwd_v3_strided(
     (flash_attn_fwd_v3_kernel<DD, CC, DR>), \
     grid, block, 0, stream, (const bf16_t*)q, (const bf16_t*)k, \
     (const bf16_t*)v, (bf16_t*)o, lse, klens, qs, os, b, h, s, scale, dth, \
-    ksc, seed)
+    ksc, seed, (const int*)nullptr)
   if (dth) {
     if (d == 128 && causal) V3F(128, true, true);
     else if (d == 128) V3F(128, false, true);
@@ -1440,6 +1491,27 @@ extern "C" void fs_flash_attn_fwd_v3_strided(
     else V3F(64, false, false);
   }
 #undef V3F
+}
+
+// Causal forward with a per-row key start (kstart [b, s] int32, see
+// v3_kstart_at); no dropout, no klens.
+extern "C" void fs_flash_attn_fwd_v3_kstart(
+    const void* q, const void* k, const void* v, void* o, float* lse,
+    const int* kstart, const long* qs3, const long* os3, int b, int h, int s,
+    int d, float scale, hipStream_t stream) {
+  const FaStrides qs{qs3[0], qs3[1], qs3[2]};
+  const FaStrides os{os3[0], os3[1], os3[2]};
+  dim3 grid((s + V3_QBLK - 1) / V3_QBLK, h, b);
+  dim3 block(FA_WAVES * 64);
+#define V3K(DD) hipLaunchKernelGGL( \
+    (flash_attn_fwd_v3_kernel<DD, true, false, true>), \
+    grid, block, 0, stream, (const bf16_t*)q, (const bf16_t*)k, \
+    (const bf16_t*)v, (bf16_t*)o, lse, (const int*)nullptr, qs, os, b, h, s, \
+    scale, 0u, 1.f, 0ull, kstart)
+  if (d == 128) V3K(128);
+  else if (d == 96) V3K(96);
+  else V3K(64);
+#undef V3K
 }
 
 extern "C" void fs_flash_attn_fwd_v3(const void* q, const void* k,
@@ -1464,7 +1536,7 @@ extern "C" void fs_flash_attn_fwd_v3(const void* q, const void* k,
 #define B3_FB 32  // streamed tile width
 
 // q-major: wave owns 32 q rows (block 256), streams KV in 32-tiles.
-template <int D, bool CAUSAL, bool HAS_DROP>
+template <int D, bool CAUSAL, bool HAS_DROP, bool KS = false>
 __global__ __launch_bounds__(FA_WAVES * 64)
 void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
                                  const bf16_t* __restrict__ K,
@@ -1477,7 +1549,9 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
                                  FaStrides qs, FaStrides dos, FaStrides gs,
                                  int b, int h, int s, float scale,
                                  unsigned int drop_thresh, float keep_scale,
-                                 unsigned long long drop_seed) {
+                                 unsigned long long drop_seed,
+                                 const int* __restrict__ kstart) {
+  static_assert(!KS || (CAUSAL && !HAS_DROP), "kstart: causal, no dropout");
   constexpr int NC = D / 16;
   constexpr int NTO = D / 32;
   constexpr int SWB = fa_swb(D);
@@ -1527,6 +1601,14 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
   }
   const float lse_r = lse[my_q];
   const float dlt_r = dlt[my_q];
+  // KS: as in the forward kernel, in 32-key tiles
+  int ks_q = 0, ks_w = 0, kt0 = 0;
+  if (KS) {
+    const int* ksb = kstart + (long)blockIdx.z * s;
+    ks_q = v3_kstart_at(ksb, my_q);
+    ks_w = v3_wave_min(ks_q);
+    kt0 = v3_block_kstart_min(ksb, blockIdx.x, lane, s) / B3_FB;
+  }
 
   f32x16 dq_acc[NTO];
 #pragma unroll
@@ -1552,7 +1634,7 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
   const int st_off = v3_off<SWB>(st_r, st_c >> 3);
   bf16x8 k_reg, v_reg;
   {
-    const long krg = min(st_r, s - 1);
+    const long krg = KS ? min(kt0 * B3_FB + st_r, s - 1) : min(st_r, s - 1);
     k_reg = *reinterpret_cast<const bf16x8*>(Kp + krg * qs.r + st_c);
     v_reg = *reinterpret_cast<const bf16x8*>(Vp + krg * qs.r + st_c);
   }
@@ -1569,7 +1651,7 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
   const int q_last_w = __builtin_amdgcn_readfirstlane(q0c) + 31;
 
   int cur = 0;
-  for (int kt = 0; kt < n_kv_tiles; ++kt) {
+  for (int kt = KS ? kt0 : 0; kt < n_kv_tiles; ++kt) {
     const int k_base = kt * B3_FB;
     __syncthreads();  // publishes buf[cur]; everyone done with buf[cur^1]
     if (kt + 1 < n_kv_tiles) {
@@ -1578,7 +1660,7 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
       v_reg = *reinterpret_cast<const bf16x8*>(Vp + krg * qs.r + st_c);
     }
 
-    if (!CAUSAL || k_base <= q_last_w) {
+    if ((!CAUSAL || k_base <= q_last_w) && (!KS || k_base + B3_FB > ks_w)) {
       // S^T = K (sQ)^T and dP^T = V dO^T : one 32x32 kv-tile each
       f32x16 st, dpt;
 #pragma unroll
@@ -1608,7 +1690,8 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
         for (int j = 0; j < 4; ++j) {
           const int r = g * 4 + j;
           const int kcol = k_base + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          const bool masked = CAUSAL ? (kcol > my_q) : (kcol >= klen);
+          const bool masked = CAUSAL ? (kcol > my_q || (KS && kcol < ks_q))
+                                     : (kcol >= klen);
           float pv = masked ? 0.f : __expf(st[r] - lse_r);
           float dpv = dpt[r];
           if (HAS_DROP && drop_thresh) {
@@ -1666,7 +1749,12 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
 // VGPRs next to the 128 of dK/dV), which puts the kernel at the 256-VGPR
 // cap: a few loop-invariant values live in scratch.
 // The softmax scale folds into the exp (st*scale - lse) so K stays raw.
-template <int D, bool CAUSAL, bool HAS_DROP>
+// KS: the query loop of a block ends at the last row that still sees one of
+// its keys.  qend [b, s/64] int32 holds, per 64-key tile, the last row i
+// with kstart[i] <= the tile's last key (kstart is non-decreasing, so the
+// wrapper finds it with a searchsorted); the block takes the largest of
+// its four tiles' entries, clamped into [the block's first row, s - 1].
+template <int D, bool CAUSAL, bool HAS_DROP, bool KS = false>
 __global__ __launch_bounds__(FA_WAVES * 64)
 void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
                                   const bf16_t* __restrict__ K,
@@ -1680,7 +1768,10 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
                                   FaStrides qs, FaStrides dos, FaStrides gs,
                                   int b, int h, int s, float scale,
                                   unsigned int drop_thresh, float keep_scale,
-                                  unsigned long long drop_seed) {
+                                  unsigned long long drop_seed,
+                                  const int* __restrict__ kstart,
+                                  const int* __restrict__ qend) {
+  static_assert(!KS || (CAUSAL && !HAS_DROP), "kstart: causal, no dropout");
   constexpr int NC = D / 16;
   constexpr int NTO = D / 32;
   constexpr int SWB = fa_swb(D);
@@ -1734,7 +1825,18 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
   }
 
   const int first_qt = CAUSAL ? kv0_blk / B3_FB : 0;
-  const int n_q_tiles = s / B3_FB;
+  int n_q_tiles = s / B3_FB;
+  const int* ksb = nullptr;
+  if (KS) {
+    ksb = kstart + (long)blockIdx.z * s;
+    const int nt = s / V3_KVBLK;
+    const int* qe = qend + (long)blockIdx.z * nt;
+    int e = 0;
+#pragma unroll
+    for (int j = 0; j < V3_QBLK / V3_KVBLK; ++j)
+      e = max(e, qe[min(kv0_blk / V3_KVBLK + j, nt - 1)]);
+    n_q_tiles = min(max(e, kv0_blk), s - 1) / B3_FB + 1;
+  }
 
   // staging: one 16-byte chunk of Q and of dO per thread (B3_FB * D / 8
   // <= 512 chunks)
@@ -1786,6 +1888,8 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
     const int qcol = q_base + ln;
     const float lse_c = lse[qcol];
     const float dlt_c = dlt[qcol];
+    int ks_c = 0;
+    if (KS) ks_c = v3_kstart_at(ksb, qcol);
     __syncthreads();
 
     // St = K Q^T (raw K; scale folded into the exp below)
@@ -1820,7 +1924,8 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
       for (int j = 0; j < 4; ++j) {
         const int r = g * 4 + j;
         const int kvrow = kv0c + (r & 3) + 8 * (r >> 2) + 4 * hi;
-        const bool masked = CAUSAL ? (qcol < kvrow) : (kvrow >= klen);
+        const bool masked = CAUSAL ? (qcol < kvrow || (KS && kvrow < ks_c))
+                                   : (kvrow >= klen);
         float pv = masked ? 0.f : __expf(st[r] * scale - lse_c);
         float dm = 1.f;
         if (HAS_DROP && drop_thresh) {
@@ -1881,14 +1986,16 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
   }
 }
 
-template <int D, bool CAUSAL, bool HAS_DROP>
+template <int D, bool CAUSAL, bool HAS_DROP, bool KS = false>
 static void launch_bwd_v3(const void* q, const void* k, const void* v,
                           const void* o, const void* dout, const float* lse,
                           void* dq, void* dk, void* dv, float* delta_ws,
                           const int* klens, FaStrides qs, FaStrides os,
                           FaStrides dos, FaStrides gs, int b, int h, int s,
                           float scale, unsigned int dth, float ksc,
-                          unsigned long long seed, hipStream_t stream) {
+                          unsigned long long seed, hipStream_t stream,
+                          const int* kstart = nullptr,
+                          const int* qend = nullptr) {
   {
     // at most 16 x-blocks per (batch, head): plenty of blocks to fill the
     // chip while each wave still streams several rows
@@ -1900,16 +2007,16 @@ static void launch_bwd_v3(const void* q, const void* k, const void* v,
   }
   dim3 grid((s + V3_QBLK - 1) / V3_QBLK, h, b);
   dim3 block(FA_WAVES * 64);
-  hipLaunchKernelGGL((flash_attn_bwd_dq_v3_kernel<D, CAUSAL, HAS_DROP>),
+  hipLaunchKernelGGL((flash_attn_bwd_dq_v3_kernel<D, CAUSAL, HAS_DROP, KS>),
                      grid, block, 0, stream, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout,
                      lse, delta_ws, (bf16_t*)dq, klens, qs, dos, gs, b, h, s,
-                     scale, dth, ksc, seed);
-  hipLaunchKernelGGL((flash_attn_bwd_dkv_v3_kernel<D, CAUSAL, HAS_DROP>),
+                     scale, dth, ksc, seed, kstart);
+  hipLaunchKernelGGL((flash_attn_bwd_dkv_v3_kernel<D, CAUSAL, HAS_DROP, KS>),
                      grid, block, 0, stream, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout,
                      lse, delta_ws, (bf16_t*)dk, (bf16_t*)dv, klens, qs, dos,
-                     gs, b, h, s, scale, dth, ksc, seed);
+                     gs, b, h, s, scale, dth, ksc, seed, kstart, qend);
 }
 
 // qs3: q|k|v, os3: o, dos3: dout, gs3: dq|dk|dv (batch, head, row) strides.
@@ -1946,6 +2053,28 @@ extern "C" void fs_flash_attn_bwd_v3_strided(
     else BWD3(64, false, false);
   }
 #undef BWD3
+}
+
+// Causal backward with a per-row key start; qend [b, s/64] int32 is the
+// query-loop bound of dkv (see flash_attn_bwd_dkv_v3_kernel).  delta does
+// not depend on the mask, so flash_delta_v3_kernel serves both.
+extern "C" void fs_flash_attn_bwd_v3_kstart(
+    const void* q, const void* k, const void* v, const void* o,
+    const void* dout, const float* lse, void* dq, void* dk, void* dv,
+    float* delta_ws, const int* kstart, const int* qend, const long* qs3,
+    const long* os3, const long* dos3, const long* gs3, int b, int h, int s,
+    int d, float scale, hipStream_t stream) {
+  const FaStrides qs{qs3[0], qs3[1], qs3[2]};
+  const FaStrides os{os3[0], os3[1], os3[2]};
+  const FaStrides dos{dos3[0], dos3[1], dos3[2]};
+  const FaStrides gs{gs3[0], gs3[1], gs3[2]};
+#define BWD3K(DD) launch_bwd_v3<DD, true, false, true>( \
+      q, k, v, o, dout, lse, dq, dk, dv, delta_ws, nullptr, qs, os, dos, gs, \
+      b, h, s, scale, 0u, 1.f, 0ull, stream, kstart, qend)
+  if (d == 128) BWD3K(128);
+  else if (d == 96) BWD3K(96);
+  else BWD3K(64);
+#undef BWD3K
 }
 
 extern "C" void fs_flash_attn_bwd_v3(const void* q, const void* k,

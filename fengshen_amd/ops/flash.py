@@ -7,10 +7,16 @@ generality (ref flash_attention.py:174 call semantics):
   masks become klens int32 [b]);
 - cross-attention (sq != sk, ragged sk) for the SD UNet;
 - head_dim in {40, 64, 80, 96, 128, 160} (BERT 64, GPT2-3.5B 96,
-  LLaMA 128, SD 40/80/160).
+  LLaMA 128, SD 40/80/160);
+- causal with a per-row key start (``kstart`` int32 [b, s]: row i sees
+  keys kstart[i] <= j <= i) for padded and packed batches: right padding
+  (0), left padding by p (p), packed documents (start of the row's
+  document); a pad row sees only itself (kstart[i] = i).  v3 shapes only,
+  no dropout.
 """
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -34,17 +40,130 @@ def _v3_eligible(ext, q, k, causal, klens, dropout_p):
             and q.shape[-2] % 64 == 0 and q.shape[-2] >= 64):
         return False
     if dropout_p > 0:
-        import os
         return os.environ.get("FENGSHEN_FLASH_V3_DROP") == "1" \
             and q.shape[-1] in (64, 96)
     return True
 
 
+def varlen_flash_enabled() -> bool:
+    """FENGSHEN_VARLEN_FLASH=0 keeps causal attention under a mask on the
+    bmm + masked-softmax path."""
+    return os.environ.get("FENGSHEN_VARLEN_FLASH", "1") != "0"
+
+
+def kstart_supported(head_dim: int, sq: int, sk: int, dtype,
+                     dropout_p: float) -> bool:
+    """Shapes the kstart kernels cover."""
+    return (dtype == torch.bfloat16 and head_dim in (64, 96, 128)
+            and sq == sk and sq % 64 == 0 and sq >= 64 and dropout_p == 0)
+
+
+def kstart_qend(kstart: torch.Tensor) -> torch.Tensor:
+    """Query-loop bound of the dkv kernel: int32 [b, s/64], entry t = the
+    last row i with kstart[i] <= 64*t + 63 (the last key of 64-key tile t).
+    kstart must be non-decreasing along s, so this is a searchsorted; it
+    runs on kstart's device with no host sync."""
+    b, s = kstart.shape
+    last_key = torch.arange(63, s, 64, device=kstart.device,
+                            dtype=kstart.dtype)
+    pos = torch.searchsorted(kstart, last_key.unsqueeze(0).expand(b, -1)
+                             .contiguous(), right=True)
+    return (pos - 1).to(torch.int32)
+
+
+def kstart_to_mask(kstart: torch.Tensor) -> torch.Tensor:
+    """The dense [b, 1, s, s] bool mask (True = masked) kstart stands for."""
+    s = kstart.shape[1]
+    ar = torch.arange(s, device=kstart.device)
+    i, j = ar.view(1, s, 1), ar.view(1, 1, s)
+    return ((j > i) | (j < kstart.unsqueeze(2))).unsqueeze(1)
+
+
+def kstart_from_eod(tokens: torch.Tensor, eod_token: int) -> torch.Tensor:
+    """int32 [b, s] key start of a packed batch: a document ends with its
+    EOD token and the next one starts behind it, as with
+    get_ltor_masks_and_position_ids(reset_attention_mask=True) — whose
+    [b, 1, s, s] mask is kstart_to_mask of this and is never built here."""
+    b, s = tokens.shape
+    ar = torch.arange(s, device=tokens.device)
+    # start of the document that follows an EOD at j is j + 1; a row's
+    # start is the latest one at or before it
+    starts = torch.where(tokens == eod_token, ar + 1, torch.zeros_like(ar))
+    starts = torch.cat([starts.new_zeros(b, 1), starts[:, :-1]], dim=1)
+    return torch.cummax(starts, dim=1).values.to(torch.int32)
+
+
+def mask_to_kstart(mask: torch.Tensor, s: int) -> Optional[torch.Tensor]:
+    """Convert a True=masked mask of causal self-attention over s tokens
+    into a per-row key start (int32 [b, s]), or None if it is not one:
+    - [b, s] or [b, 1, 1, s] key-pad mask whose kept keys form one
+      contiguous run per batch row (left, right or no padding).  Real rows
+      start at the run's first key; pad rows see only themselves.
+    - [b, 1, s, s] mask that is exactly "j > i or j < kstart[i]" with a
+      non-decreasing kstart (packed documents).
+    The candidate is verified by rebuilding the mask from it."""
+    if mask.dtype != torch.bool:
+        mask = mask != 0
+    ar = torch.arange(s, device=mask.device)
+    if mask.dim() == 4 and mask.shape[1] == 1 and mask.shape[2] == s \
+            and mask.shape[3] == s and s > 1:
+        keep = ~mask[:, 0]
+        ks = keep.to(torch.int8).argmax(dim=2)        # first kept key
+        cand = ((ar.view(1, 1, s) > ar.view(1, s, 1))
+                | (ar.view(1, 1, s) < ks.unsqueeze(2)))
+        if not torch.equal(cand, mask[:, 0]):
+            return None
+        if not bool((ks[:, 1:] >= ks[:, :-1]).all()):
+            return None
+        return ks.to(torch.int32).contiguous()
+    if mask.dim() == 4:
+        if mask.shape[1] != 1 or mask.shape[2] != 1 or mask.shape[3] != s:
+            return None
+        m2 = mask[:, 0, 0, :]
+    elif mask.dim() == 2 and mask.shape[1] == s:
+        m2 = mask
+    else:
+        return None
+    keep = ~m2
+    n = keep.sum(dim=1)
+    first = keep.to(torch.int8).argmax(dim=1)
+    run = (ar.unsqueeze(0) >= first.unsqueeze(1)) \
+        & (ar.unsqueeze(0) < (first + n).unsqueeze(1))
+    if not torch.equal(run, keep):
+        return None  # holes between the keys
+    ks = torch.where(keep, first.unsqueeze(1), ar.unsqueeze(0))
+    return ks.to(torch.int32).contiguous()
+
+
+def model_kstart(mask: Optional[torch.Tensor], x: torch.Tensor
+                 ) -> Optional[torch.Tensor]:
+    """For a model's forward: convert its causal ``mask`` once for all
+    layers (mask_to_kstart compares on the device and reads the verdict
+    back) when the hidden states x [b, s, h] can reach the kstart kernels
+    at all; the layers still check head dim and dropout for themselves and
+    keep the mask for what the kernels do not cover."""
+    if mask is None or not varlen_flash_enabled():
+        return None
+    s = x.shape[1]
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and s % 64 == 0
+            and s >= 64 and mask.shape[-1] == s):
+        return None
+    return mask_to_kstart(mask, s)
+
+
 class _FlashAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, scale, causal, klens, dropout_p, seed):
+    def forward(ctx, q, k, v, scale, causal, klens, dropout_p, seed,
+                kstart=None):
         ext = get_ext()
-        if _v3_eligible(ext, q, k, causal, klens, dropout_p):
+        ctx.kstart = kstart
+        if kstart is not None:
+            # no quiet fall-back: the binding raises on anything the
+            # kstart kernels do not cover
+            o, lse = ext.flash_attn_fwd_v3(q, k, v, scale, causal, klens,
+                                           dropout_p, seed, kstart=kstart)
+            ctx.qend = kstart_qend(kstart)
+        elif _v3_eligible(ext, q, k, causal, klens, dropout_p):
             o, lse = ext.flash_attn_fwd_v3(q, k, v, scale, causal, klens,
                                            dropout_p, seed)
         else:
@@ -62,7 +181,12 @@ class _FlashAttention(torch.autograd.Function):
     def backward(ctx, do):
         q, k, v, o, lse = ctx.saved_tensors
         ext = get_ext()
-        if _v3_eligible(ext, q, k, ctx.causal, ctx.klens, ctx.dropout_p):
+        if ctx.kstart is not None:
+            dq, dk, dv = ext.flash_attn_bwd_v3(
+                q, k, v, o, do.contiguous(), lse, ctx.scale, ctx.causal,
+                ctx.klens, ctx.dropout_p, ctx.seed, kstart=ctx.kstart,
+                qend=ctx.qend)
+        elif _v3_eligible(ext, q, k, ctx.causal, ctx.klens, ctx.dropout_p):
             dq, dk, dv = ext.flash_attn_bwd_v3(
                 q, k, v, o, do.contiguous(), lse, ctx.scale, ctx.causal,
                 ctx.klens, ctx.dropout_p, ctx.seed)
@@ -70,7 +194,7 @@ class _FlashAttention(torch.autograd.Function):
             dq, dk, dv = ext.flash_attn_bwd(
                 q, k, v, o, do.contiguous(), lse, ctx.scale, ctx.causal,
                 ctx.klens, ctx.dropout_p, ctx.seed)
-        return dq, dk, dv, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None
 
 
 def _thirds(qkv, num_heads):
@@ -120,13 +244,19 @@ class _PackedFlash(torch.autograd.Function):
     gradient.  No layout copies, no ``cat``."""
 
     @staticmethod
-    def forward(ctx, qkv, num_heads, scale, causal, klens):
+    def forward(ctx, qkv, num_heads, scale, causal, klens, kstart=None):
         b, s, w = qkv.shape
         q, k, v = _thirds(qkv, num_heads)
         o = torch.empty(b, s, w // 3, dtype=qkv.dtype, device=qkv.device)
-        lse = get_ext().flash_attn_fwd_v3_strided(
-            q, k, v, o.unflatten(2, (num_heads, -1)).transpose(1, 2), scale,
-            causal, klens)
+        ov = o.unflatten(2, (num_heads, -1)).transpose(1, 2)
+        if kstart is not None:
+            lse = get_ext().flash_attn_fwd_v3_strided(
+                q, k, v, ov, scale, causal, klens, kstart=kstart)
+            ctx.qend = kstart_qend(kstart)
+        else:
+            lse = get_ext().flash_attn_fwd_v3_strided(q, k, v, ov, scale,
+                                                      causal, klens)
+        ctx.kstart = kstart
         ctx.save_for_backward(qkv, o, lse)
         ctx.num_heads = num_heads
         ctx.scale = scale
@@ -145,21 +275,24 @@ class _PackedFlash(torch.autograd.Function):
             do = do.contiguous()
         grad = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
         dq, dk, dv = _thirds(grad, np_)
+        kw = {}
+        if ctx.kstart is not None:
+            kw = {"kstart": ctx.kstart, "qend": ctx.qend}
         get_ext().flash_attn_bwd_v3_strided(
             q, k, v, o.unflatten(2, (np_, -1)).transpose(1, 2),
             do.unflatten(2, (np_, -1)).transpose(1, 2), lse, dq, dk, dv,
-            ctx.scale, ctx.causal, ctx.klens)
-        return grad, None, None, None, None
+            ctx.scale, ctx.causal, ctx.klens, **kw)
+        return grad, None, None, None, None, None
 
 
 def packed_attn_eligible(qkv, head_dim: int, causal: bool, mask,
                          dropout_p: float) -> bool:
     """True when self-attention can run on the packed [b, s, 3*np*hn]
     projection output in place: v3 shapes (d in {64, 96, 128}, s % 64 == 0),
-    bf16, no dropout, and no mask under causal (a bidirectional mask must
-    still reduce to klens — checked by the caller).  FENGSHEN_PACKED_ATTN=0
+    bf16, no dropout.  A mask must still reduce to klens (bidirectional)
+    or to kstart (causal) — checked by the caller; under causal a mask is
+    refused outright when FENGSHEN_VARLEN_FLASH=0.  FENGSHEN_PACKED_ATTN=0
     forces the chunk/transpose/contiguous path."""
-    import os
     if os.environ.get("FENGSHEN_PACKED_ATTN", "1") == "0":
         return False
     if qkv.dtype != torch.bfloat16 or qkv.dim() != 3 or dropout_p > 0:
@@ -167,7 +300,7 @@ def packed_attn_eligible(qkv, head_dim: int, causal: bool, mask,
     s = qkv.shape[1]
     if head_dim not in (64, 96, 128) or s % 64 != 0 or s < 64:
         return False
-    if causal and mask is not None:
+    if causal and mask is not None and not varlen_flash_enabled():
         return False
     return (qkv.stride(2) == 1 and qkv.stride(0) % 8 == 0
             and qkv.stride(1) % 8 == 0 and qkv.storage_offset() % 8 == 0)
@@ -177,15 +310,18 @@ def packed_self_attention(qkv: torch.Tensor, num_heads: int,
                           cos: Optional[torch.Tensor],
                           sin: Optional[torch.Tensor], offset: int,
                           scale: float, causal: bool = True,
-                          klens: Optional[torch.Tensor] = None
+                          klens: Optional[torch.Tensor] = None,
+                          kstart: Optional[torch.Tensor] = None
                           ) -> torch.Tensor:
     """qkv [b, s, 3*np*hn] bf16, partition-local layout [q | k | v], last dim
     unit-stride.  Rotates q/k IN PLACE when cos/sin are given (pass None
     for no rotary) and returns the context as [b, s, np*hn], ready for the
-    output projection.  Callers must not reuse ``qkv`` afterwards."""
+    output projection.  Callers must not reuse ``qkv`` afterwards.
+    ``kstart`` (int32 [b, s], causal only): per-row key start."""
     if cos is not None:
         qkv = _RopePackedInplace.apply(qkv, num_heads, cos, sin, offset)
-    return _PackedFlash.apply(qkv, num_heads, float(scale), causal, klens)
+    return _PackedFlash.apply(qkv, num_heads, float(scale), causal, klens,
+                              kstart)
 
 
 def _draw_seed(device) -> int:
@@ -205,15 +341,18 @@ def _draw_seed(device) -> int:
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                     scale: float, causal: bool = True,
                     klens: Optional[torch.Tensor] = None,
-                    dropout_p: float = 0.0) -> torch.Tensor:
+                    dropout_p: float = 0.0,
+                    kstart: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q [b,h,sq,d], k/v [b,h,sk,d] bf16 contiguous.  dropout_p > 0
     applies attention dropout with an in-kernel counter hash (no mask
     tensor); the normalizer uses the undropped row sum, matching eager
-    dropout(softmax(S)) @ V."""
+    dropout(softmax(S)) @ V.  kstart (int32 [b, s], non-decreasing along
+    s): causal attention where row i sees keys kstart[i] <= j <= i; v3
+    shapes, no dropout — anything else raises."""
     seed = _draw_seed(q.device) if dropout_p > 0 else 0
     return _FlashAttention.apply(q.contiguous(), k.contiguous(),
                                  v.contiguous(), scale, causal, klens,
-                                 float(dropout_p), seed)
+                                 float(dropout_p), seed, kstart)
 
 
 def mask_to_klens(mask: torch.Tensor, sk: int) -> Optional[torch.Tensor]:

@@ -472,21 +472,41 @@ def apply_rotary(q, k, cos, sin, offset: int = 0):
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
               causal: bool = False, mask: Optional[torch.Tensor] = None,
               dropout_p: float = 0.0, training: bool = False,
-              scale: Optional[float] = None) -> torch.Tensor:
+              scale: Optional[float] = None,
+              kstart: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q,k,v: [b, np, s, hn] -> context [b, np, sq, hn].
 
     GPU path: flash-style fused HIP kernel when available (csrc/flash_attn.hip)
     else hipBLASLt bmm + fused-softmax kernel.  CPU path: eager oracle.
+
+    kstart (int32 [b, s], causal self-attention only): row i sees keys
+    kstart[i] <= j <= i (ops/flash.py).  Callers that have it pass it
+    instead of, or next to, the dense mask it stands for; a causal mask
+    given without it is converted when it is of that form.  Shapes the
+    kstart kernels do not cover run under the dense mask as before.
     """
     b, np_, sq, hn = q.shape
     sk = k.shape[-2]
     if scale is None:
         scale = 1.0 / math.sqrt(hn)
+    if kstart is not None and not (causal and sq == sk):
+        raise ValueError("kstart needs causal self-attention (sq == sk)")
     ext = get_ext() if use_hip(q) else None
     if ext is not None and hasattr(ext, "flash_attn_fwd"):
         from fengshen_amd.ops.flash import (
-            flash_attention, flash_attn_supported, mask_to_klens)
+            flash_attention, flash_attn_supported, kstart_supported,
+            mask_to_klens, mask_to_kstart, varlen_flash_enabled)
         drop = dropout_p if training else 0.0
+        if causal and (mask is not None or kstart is not None) \
+                and varlen_flash_enabled() \
+                and kstart_supported(hn, sq, sk, q.dtype, drop):
+            ks = kstart if kstart is not None else mask_to_kstart(mask, sq)
+            if ks is not None:
+                return flash_attention(q, k, v, scale, causal=True,
+                                       kstart=ks)
+        if mask is None and kstart is not None:
+            from fengshen_amd.ops.flash import kstart_to_mask
+            mask = kstart_to_mask(kstart)
         if flash_attn_supported(q, k, v, causal, mask, drop):
             if causal and mask is None:
                 return flash_attention(q, k, v, scale, causal=True,
@@ -498,6 +518,9 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                 if mask is None or klens is not None:
                     return flash_attention(q, k, v, scale, causal=False,
                                            klens=klens, dropout_p=drop)
+    if mask is None and kstart is not None:
+        from fengshen_amd.ops.flash import kstart_to_mask
+        mask = kstart_to_mask(kstart)
     # bmm path: scores in [b*np, sq, sk]
     q2 = q.reshape(b * np_, sq, hn)
     k2 = k.reshape(b * np_, sk, hn)
