@@ -130,9 +130,31 @@ def get_norm(kind: str, dim: int, eps: float, dtype=None) -> nn.Module:
     raise ValueError(kind)
 
 
+def check_kv_heads(num_heads: int, num_kv_heads: int, tp: int) -> None:
+    """Grouped-query head counts: the query heads split evenly over the KV
+    heads and the KV heads over the tensor-parallel ranks (KV heads are not
+    replicated across ranks)."""
+    if num_kv_heads < 1 or num_heads % num_kv_heads:
+        raise ValueError(f"num_heads ({num_heads}) must be a multiple of "
+                         f"num_kv_heads ({num_kv_heads})")
+    if num_kv_heads % tp:
+        raise ValueError(f"num_kv_heads ({num_kv_heads}) must be divisible "
+                         f"by the tensor-parallel size ({tp})")
+
+
 class ParallelAttention(nn.Module):
     """Multi-head attention with fused QKV column-parallel in, row-parallel
-    out (ref ParallelSelfAttention, transformer.py:175-474)."""
+    out (ref ParallelSelfAttention, transformer.py:175-474).
+
+    num_kv_heads < num_heads is grouped-query attention (1 = multi-query):
+    query head j uses KV head j // (num_heads / num_kv_heads), HF's
+    ``repeat_kv`` order.  The projection output is [q | k | v] with widths
+    [h*d, h_kv*d, h_kv*d] (per partition under tensor parallelism, which
+    needs h_kv % tp == 0), the KV cache stores h_kv heads, and causal
+    layers run the grouped-query flash kernels on it (ops/flash.py);
+    F_ops.attention expands K/V where those do not apply.  Block-sparse
+    layers expand K/V to h heads in front of SparseSelfAttention: the
+    sparse kernels have no grouped-query form."""
 
     def __init__(self, hidden_size: int, num_heads: int, *, causal: bool,
                  rotary: bool = False, rope_base: float = 10000.0,
@@ -151,9 +173,10 @@ class ParallelAttention(nn.Module):
         self.hidden_size = hidden_size
         self.num_heads = num_heads
         self.num_kv_heads = num_kv_heads or num_heads
-        assert self.num_kv_heads == num_heads, "GQA arrives with kernel pass 2"
+        check_kv_heads(num_heads, self.num_kv_heads, tp)
         self.head_dim = divide(hidden_size, num_heads)
         self.num_heads_per_partition = divide(num_heads, tp)
+        self.num_kv_heads_per_partition = self.num_kv_heads // tp
         self.causal = causal
         self.rotary = rotary
         self.attention_dropout = attention_dropout
@@ -163,7 +186,8 @@ class ParallelAttention(nn.Module):
         output_init_method = output_init_method or init_method
 
         self.qkv_proj = MergedColumnParallelLinear(
-            hidden_size, [hidden_size, hidden_size, hidden_size], bias=bias,
+            hidden_size, [hidden_size, self.num_kv_heads * self.head_dim,
+                          self.num_kv_heads * self.head_dim], bias=bias,
             init_method=init_method, dtype=dtype)
         self.out_proj = RowParallelLinear(
             hidden_size, hidden_size, bias=bias, input_is_parallel=True,
@@ -224,13 +248,13 @@ class ParallelAttention(nn.Module):
         np_ = self.num_heads_per_partition
         hn = self.head_dim
         keep = self._sparse_keep_mask(attention_mask, b, sq)
-        q, k, v = qkv.chunk(3, dim=-1)
-        q = q.view(b, sq, np_, hn).transpose(1, 2)
-        k = k.view(b, sq, np_, hn).transpose(1, 2)
-        v = v.view(b, sq, np_, hn).transpose(1, 2)
+        q, k, v = self._split_heads(qkv)
         if self.rotary:
             cos, sin = self._rope_tables(q.device, sq)
             q, k = F_ops.apply_rotary(q, k, cos, sin, offset=0)
+        if self.num_kv_heads_per_partition != np_:
+            from fengshen_amd.ops.flash import expand_kv
+            k, v = expand_kv(k, np_), expand_kv(v, np_)
         ctx = self.sparse_attn(q.contiguous(), k.contiguous(), v.contiguous(),
                                attention_mask=keep, scale=self.norm_factor)
         ctx = ctx.transpose(1, 2).reshape(b, sq, np_ * hn)
@@ -238,6 +262,17 @@ class ParallelAttention(nn.Module):
         if isinstance(out, tuple) and self.reduce_output:
             out = out[0]
         return out
+
+    def _split_heads(self, qkv):
+        """[b, s, (np + 2*nkv)*hn] -> q [b, np, s, hn], k/v [b, nkv, s, hn]
+        views."""
+        b, sq, _ = qkv.shape
+        np_, nkv = self.num_heads_per_partition, self.num_kv_heads_per_partition
+        hn = self.head_dim
+        q, k, v = qkv.split([np_ * hn, nkv * hn, nkv * hn], dim=-1)
+        return (q.view(b, sq, np_, hn).transpose(1, 2),
+                k.view(b, sq, nkv, hn).transpose(1, 2),
+                v.view(b, sq, nkv, hn).transpose(1, 2))
 
     def _rope_tables(self, device, seq_needed: int):
         cache = self._rope_cache
@@ -262,7 +297,8 @@ class ParallelAttention(nn.Module):
         np_ = self.num_heads_per_partition
         hn = self.head_dim
 
-        qkv = self.qkv_proj(x)  # [b, sq, 3h/tp]
+        nkv = self.num_kv_heads_per_partition
+        qkv = self.qkv_proj(x)  # [b, sq, (np + 2*nkv)*hn]
 
         if self.sparse_attn is not None:
             return self._sparse_forward(qkv, attention_mask, cache)
@@ -277,7 +313,7 @@ class ParallelAttention(nn.Module):
             masked = attention_mask is not None or kstart is not None
             if packed_attn_eligible(qkv, hn, self.causal,
                                     attention_mask if kstart is None
-                                    else kstart, drop):
+                                    else kstart, drop, np_, nkv):
                 klens = ks = None
                 if self.causal and masked and varlen_flash_enabled():
                     ks = kstart if kstart is not None else \
@@ -290,17 +326,15 @@ class ParallelAttention(nn.Module):
                         cos, sin = self._rope_tables(qkv.device, sq)
                     ctx = packed_self_attention(
                         qkv, np_, cos, sin, 0, self.norm_factor,
-                        causal=self.causal, klens=klens, kstart=ks)
+                        causal=self.causal, klens=klens, kstart=ks,
+                        num_kv_heads=nkv)
                     out = self.out_proj(ctx)
                     if isinstance(out, tuple) and self.reduce_output:
                         out = out[0]
                     return out
 
-        q, k, v = qkv.chunk(3, dim=-1)
-        # [b, s, np, hn] -> [b, np, s, hn]
-        q = q.view(b, sq, np_, hn).transpose(1, 2)
-        k = k.view(b, sq, np_, hn).transpose(1, 2)
-        v = v.view(b, sq, np_, hn).transpose(1, 2)
+        # [b, s, n, hn] -> [b, n, s, hn]
+        q, k, v = self._split_heads(qkv)
 
         offset = 0
         if cache is not None:
@@ -406,7 +440,8 @@ class ParallelTransformerLayer(nn.Module):
                  dtype=None, layer_idx: int = 0,
                  parallel_residual: bool = False,
                  attention_type: str = "global",
-                 sparsity_config: Optional[dict] = None):
+                 sparsity_config: Optional[dict] = None,
+                 num_kv_heads: Optional[int] = None):
         super().__init__()
         # parallel_residual: GPT-J composition x + attn(ln1 x) + mlp(ln2 x)
         # with ONE deferred TP all-reduce over the summed partials
@@ -420,7 +455,8 @@ class ParallelTransformerLayer(nn.Module):
             bias=bias, init_method=init_method,
             output_init_method=output_init_method, dtype=dtype,
             layer_idx=layer_idx, reduce_output=not parallel_residual,
-            attention_type=attention_type, sparsity_config=sparsity_config)
+            attention_type=attention_type, sparsity_config=sparsity_config,
+            num_kv_heads=num_kv_heads)
         self.post_attention_norm = get_norm(norm, hidden_size, norm_eps, dtype)
         if mlp_type == "swiglu":
             self.mlp = LLaMAParallelMLP(

@@ -31,7 +31,12 @@ class LlamaConfig(PretrainedConfig):
                  torch_dtype="bfloat16",
                  attention_config=None,
                  sparsity_config=None,
+                 num_key_value_heads=None,
                  **kwargs):
+        # grouped-query attention (HF's name): KV heads shared by
+        # num_attention_heads / num_key_value_heads query heads each;
+        # None = one per query head
+        self.num_key_value_heads = num_key_value_heads or num_attention_heads
         # per-layer attention types, [[types, repeat], ...] as taken by
         # layers.expand_attention_types (None = all "global"), and the
         # sparsity_config dict of ops.sparse_attention
@@ -62,6 +67,16 @@ def ziya_llama_13b_config(**over) -> LlamaConfig:
     cfg = dict(vocab_size=39424, hidden_size=5120, num_hidden_layers=40,
                num_attention_heads=40, intermediate_size=13824,
                max_position_embeddings=2048)
+    cfg.update(over)
+    return LlamaConfig(**cfg)
+
+
+def llama3_8b_config(**over) -> LlamaConfig:
+    """Llama-3-8B shape: grouped-query attention, 4 query heads per KV head."""
+    cfg = dict(vocab_size=128256, hidden_size=4096, num_hidden_layers=32,
+               num_attention_heads=32, num_key_value_heads=8,
+               intermediate_size=14336, max_position_embeddings=8192,
+               rotary_emb_base=500000.0)
     cfg.update(over)
     return LlamaConfig(**cfg)
 

@@ -74,7 +74,8 @@ class LlamaModel(LlamaPreTrainedModel):
                 parallel_residual=getattr(config, "parallel_residual",
                                           False),
                 attention_type=attn_types[i],
-                sparsity_config=getattr(config, "sparsity_config", None))
+                sparsity_config=getattr(config, "sparsity_config", None),
+                num_kv_heads=getattr(config, "num_key_value_heads", None))
             for i in range(config.num_hidden_layers)])
         self.norm = RMSNorm(config.hidden_size, eps=config.rms_norm_epsilon)
         self.gradient_checkpointing = False

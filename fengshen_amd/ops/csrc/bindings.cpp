@@ -60,7 +60,7 @@ void fs_bf16_gemv(const void*, const void*, void*, int, int, int,
 void fs_add_rms_norm(const void*, const void*, const void*, void*, void*,
                      int, int, float, hipStream_t);
 void fs_decode_attn(const void*, void*, void*, const float*, const float*,
-                    const void*, void*, int, int, int, int, float, int,
+                    const void*, void*, int, int, int, int, int, float, int,
                     hipStream_t);
 void fs_w8_gemv(const void*, const float*, const void*, void*, int, int, int,
                 hipStream_t);
@@ -94,6 +94,16 @@ void fs_flash_attn_bwd_v3_kstart(const void*, const void*, const void*,
                                  const int*, const long*, const long*,
                                  const long*, const long*, int, int, int, int,
                                  float, hipStream_t);
+void fs_flash_attn_fwd_v3_gqa(const void*, const void*, const void*, void*,
+                              float*, const int*, const long*, const long*,
+                              const long*, int, int, int, int, int, float,
+                              hipStream_t);
+void fs_flash_attn_bwd_v3_gqa(const void*, const void*, const void*,
+                              const void*, const void*, const float*, void*,
+                              void*, void*, float*, const int*, const int*,
+                              const long*, const long*, const long*,
+                              const long*, const long*, const long*, int, int,
+                              int, int, int, float, hipStream_t);
 void fs_rope_inplace(void*, void*, const float*, const float*, int, int, int,
                      int, long, long, long, int, int, int, hipStream_t);
 int fs_fused_norm_vectors(int);
@@ -495,6 +505,22 @@ static void strides3(const at::Tensor& t, long out[3]) {
   out[2] = t.stride(2);
 }
 
+// Grouped-query attention: k/v (and dk/dv) carry h_kv = k.size(1) heads,
+// query head j uses KV head j / (h / h_kv).  Returns h_kv after checking
+// what the GQA instantiations do not cover; h_kv == h takes none of this.
+static int checked_kv_heads(const at::Tensor& k, int h, bool causal,
+                            double drop_p, bool has_klens) {
+  TORCH_CHECK(k.dim() == 4, "k must be [b, h_kv, s, d]");
+  const int h_kv = k.size(1);
+  if (h_kv == h) return h;
+  TORCH_CHECK(h_kv >= 1 && h % h_kv == 0, "flash v3 GQA: ", h,
+              " query heads are not a multiple of ", h_kv, " KV heads");
+  TORCH_CHECK(causal, "flash v3 GQA: causal=True only");
+  TORCH_CHECK(drop_p == 0.0, "flash v3 GQA: dropout is not supported");
+  TORCH_CHECK(!has_klens, "flash v3 GQA: klens is not supported");
+  return h_kv;
+}
+
 static const int* checked_klens(const c10::optional<at::Tensor>& klens,
                                 bool causal, int b) {
   if (!klens.has_value()) return nullptr;
@@ -571,12 +597,13 @@ static at::Tensor flash_attn_fwd_v3_strided(
   const int b = q.size(0), h = q.size(1), s = q.size(2), d = q.size(3);
   TORCH_CHECK((d == 128 || d == 96 || d == 64) && s % 64 == 0 && s >= 64,
               "flash v3: d in {64, 96, 128}, s a multiple of 64");
+  const int h_kv = checked_kv_heads(k, h, causal, 0.0, klens.has_value());
   check_strided_view(q, "q", b, h, s, d);
-  check_strided_view(k, "k", b, h, s, d);
-  check_strided_view(v, "v", b, h, s, d);
+  check_strided_view(k, "k", b, h_kv, s, d);
+  check_strided_view(v, "v", b, h_kv, s, d);
   check_strided_view(o, "o", b, h, s, d);
-  check_same_strides(q, k, "q and k");
-  check_same_strides(q, v, "q and v");
+  if (h_kv == h) check_same_strides(q, k, "q and k");
+  check_same_strides(k, v, "k and v");
   if (kstart.has_value())
     check_kstart(*kstart, c10::nullopt, false, q, causal, 0.0,
                  klens.has_value(), check_values);
@@ -585,6 +612,16 @@ static at::Tensor flash_attn_fwd_v3_strided(
   strides3(q, qs);
   strides3(o, os);
   auto lse = at::empty({b, h, s}, q.options().dtype(at::kFloat));
+  if (h_kv != h) {
+    long kvs[3];
+    strides3(k, kvs);
+    fs_flash_attn_fwd_v3_gqa(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+        lse.data_ptr<float>(),
+        kstart.has_value() ? kstart->data_ptr<int>() : nullptr, qs, kvs, os,
+        b, h, h_kv, s, d, (float)scale, cur_stream());
+    return lse;
+  }
   if (kstart.has_value()) {
     fs_flash_attn_fwd_v3_kstart(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                                 o.data_ptr(), lse.data_ptr<float>(),
@@ -610,18 +647,21 @@ static void flash_attn_bwd_v3_strided(
   const int b = q.size(0), h = q.size(1), s = q.size(2), d = q.size(3);
   TORCH_CHECK((d == 128 || d == 96 || d == 64) && s % 64 == 0 && s >= 64,
               "flash v3: d in {64, 96, 128}, s a multiple of 64");
+  const int h_kv = checked_kv_heads(k, h, causal, 0.0, klens.has_value());
   check_strided_view(q, "q", b, h, s, d);
-  check_strided_view(k, "k", b, h, s, d);
-  check_strided_view(v, "v", b, h, s, d);
+  check_strided_view(k, "k", b, h_kv, s, d);
+  check_strided_view(v, "v", b, h_kv, s, d);
   check_strided_view(o, "o", b, h, s, d);
   check_strided_view(dout, "dout", b, h, s, d);
   check_strided_view(dq, "dq", b, h, s, d);
-  check_strided_view(dk, "dk", b, h, s, d);
-  check_strided_view(dv, "dv", b, h, s, d);
-  check_same_strides(q, k, "q and k");
-  check_same_strides(q, v, "q and v");
-  check_same_strides(dq, dk, "dq and dk");
-  check_same_strides(dq, dv, "dq and dv");
+  check_strided_view(dk, "dk", b, h_kv, s, d);
+  check_strided_view(dv, "dv", b, h_kv, s, d);
+  if (h_kv == h) {
+    check_same_strides(q, k, "q and k");
+    check_same_strides(dq, dk, "dq and dk");
+  }
+  check_same_strides(k, v, "k and v");
+  check_same_strides(dk, dv, "dk and dv");
   TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat &&
               lse.is_contiguous() && lse.numel() == (int64_t)b * h * s,
               "lse must be contiguous fp32 [b, h, s]");
@@ -637,6 +677,20 @@ static void flash_attn_bwd_v3_strided(
   strides3(dout, dos);
   strides3(dq, gs);
   auto delta = at::empty({b, h, s}, q.options().dtype(at::kFloat));
+  if (h_kv != h) {
+    long kvs[3], gkvs[3];
+    strides3(k, kvs);
+    strides3(dk, gkvs);
+    const bool ks = kstart.has_value();
+    fs_flash_attn_bwd_v3_gqa(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+        dout.data_ptr(), lse.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(),
+        dv.data_ptr(), delta.data_ptr<float>(),
+        ks ? kstart->data_ptr<int>() : nullptr,
+        ks ? qend->data_ptr<int>() : nullptr, qs, kvs, os, dos, gs, gkvs, b,
+        h, h_kv, s, d, (float)scale, cur_stream());
+    return;
+  }
   if (kstart.has_value()) {
     fs_flash_attn_bwd_v3_kstart(
         q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
@@ -678,6 +732,29 @@ static void rope_inplace(at::Tensor q, at::Tensor k, at::Tensor cos,
                   fs_dtype(q), cur_stream());
 }
 
+// One-tensor form: x is any [b, n, s, hn] view, e.g. the h + h_kv adjacent
+// q and k heads of a grouped-query packed buffer.
+static void rope_inplace_one(at::Tensor x, at::Tensor cos, at::Tensor sin,
+                             int64_t offset, bool bwd) {
+  TORCH_CHECK(x.dim() == 4, "x must be [b, n, s, hn]");
+  const int b = x.size(0), np = x.size(1), s = x.size(2), hn = x.size(3);
+  TORCH_CHECK((hn / 2) % 8 == 0 && hn % 2 == 0,
+              "head_dim/2 must be divisible by 8");
+  check_strided_view(x, "x", b, np, s, hn);
+  TORCH_CHECK(cos.is_cuda() && sin.is_cuda() &&
+              cos.scalar_type() == at::kFloat &&
+              sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
+              sin.is_contiguous() && cos.dim() == 2 && cos.size(1) == hn &&
+              sin.sizes() == cos.sizes(),
+              "cos/sin must be contiguous fp32 [S, hn]");
+  TORCH_CHECK(offset >= 0 && offset + s <= cos.size(0),
+              "rope table too short for offset + s");
+  fs_rope_inplace(x.data_ptr(), nullptr, cos.data_ptr<float>(),
+                  sin.data_ptr<float>(), b, np, s, hn, x.stride(0),
+                  x.stride(1), x.stride(2), (int)offset, bwd ? 1 : 0,
+                  fs_dtype(x), cur_stream());
+}
+
 // x [b, in] bf16, q8 [out, in] int8, scale [out] fp32 -> y [b, out] bf16
 static at::Tensor w8_gemv(at::Tensor q8, at::Tensor scale, at::Tensor x) {
   TORCH_CHECK(q8.scalar_type() == at::kChar && x.scalar_type() == at::kBFloat16);
@@ -706,9 +783,10 @@ static at::Tensor bf16_gemv(at::Tensor w, at::Tensor x) {
   return y;
 }
 
-// Fused decode step: qkv [b, 3*H] bf16, kc/vc [b, nh, L, d] bf16 caches
-// (written in-place at pos), cos/sin [max_len, d] fp32, pos [1] long.
-// Returns ctx [b, H] bf16.
+// Fused decode step: qkv [b, (nh + 2*nkv)*d] bf16, kc/vc [b, nkv, L, d] bf16
+// caches (written in-place at pos), cos/sin [max_len, d] fp32, pos [1] long.
+// nkv comes from the caches and nh from the width of qkv (nkv == nh: plain
+// multi-head attention).  Returns ctx [b, nh*d] bf16.
 static at::Tensor decode_attn(at::Tensor qkv, at::Tensor kc, at::Tensor vc,
                               at::Tensor cos_t, at::Tensor sin_t,
                               at::Tensor pos, double scale, bool rope) {
@@ -717,14 +795,23 @@ static at::Tensor decode_attn(at::Tensor qkv, at::Tensor kc, at::Tensor vc,
   TORCH_CHECK(cos_t.scalar_type() == at::kFloat &&
               sin_t.scalar_type() == at::kFloat);
   TORCH_CHECK(pos.scalar_type() == at::kLong);
-  const int b = kc.size(0), nh = kc.size(1), L = kc.size(2), d = kc.size(3);
+  TORCH_CHECK(kc.dim() == 4 && vc.sizes() == kc.sizes() &&
+                  kc.scalar_type() == at::kBFloat16 &&
+                  vc.scalar_type() == at::kBFloat16,
+              "decode_attn: caches must be bf16 [b, nkv, L, d] of one shape");
+  const int b = kc.size(0), nkv = kc.size(1), L = kc.size(2), d = kc.size(3);
   TORCH_CHECK(d == 64 || d == 128, "decode_attn: head dim must be 64/128");
-  TORCH_CHECK(qkv.numel() == (long)b * 3 * nh * d, "qkv shape mismatch");
+  const int64_t w = qkv.numel() / b - 2 * (int64_t)nkv * d;  // nh * d
+  TORCH_CHECK(qkv.numel() % b == 0 && w > 0 && w % d == 0 &&
+                  (w / d) % nkv == 0,
+              "decode_attn: qkv must be [b, (nh + 2*nkv)*d] with nh a "
+              "multiple of the caches' ", nkv, " KV heads");
+  const int nh = w / d;
   auto ctx = at::empty({b, nh * d}, qkv.options());
   fs_decode_attn(qkv.data_ptr(), kc.data_ptr(), vc.data_ptr(),
                  cos_t.data_ptr<float>(), sin_t.data_ptr<float>(),
-                 pos.data_ptr(), ctx.data_ptr(), b, nh, d, L, (float)scale,
-                 rope ? 1 : 0, cur_stream());
+                 pos.data_ptr(), ctx.data_ptr(), b, nh, nkv, d, L,
+                 (float)scale, rope ? 1 : 0, cur_stream());
   return ctx;
 }
 
@@ -934,9 +1021,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
                                   bool check_values) {
     const int b = q.size(0), h = q.size(1), s = q.size(2), d = q.size(3);
     TORCH_CHECK((d == 128 || d == 96 || d == 64) && s % 64 == 0);
-    if (kstart.has_value()) {
-      // the kstart kernels have one (strided) entry; contiguous operands
-      // are its special case and get all of its checks
+    const bool gqa =
+        checked_kv_heads(k, h, causal, drop_p, klens.has_value()) != h;
+    if (kstart.has_value() || gqa) {
+      // the kstart and GQA kernels have one (strided) entry; contiguous
+      // operands are its special case and get all of its checks
       TORCH_CHECK(drop_p == 0.0, "flash v3: kstart does not support dropout");
       TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous());
       auto dq = at::empty_like(q);
@@ -976,7 +1065,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
     const int b = q.size(0), h = q.size(1), s = q.size(2), d = q.size(3);
     TORCH_CHECK((d == 128 || d == 96 || d == 64) && s % 64 == 0 && s >= 64);
     TORCH_CHECK(k.size(2) == s, "v3 is self-attention (sq == sk)");
-    if (kstart.has_value()) {
+    const bool gqa =
+        checked_kv_heads(k, h, causal, drop_p, klens.has_value()) != h;
+    if (kstart.has_value() || gqa) {
       TORCH_CHECK(drop_p == 0.0, "flash v3: kstart does not support dropout");
       auto o = at::empty_like(q);
       auto lse = flash_attn_fwd_v3_strided(q, k, v, o, scale, causal, klens,
@@ -1011,6 +1102,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("klens"), py::arg("kstart") = py::none(),
           py::arg("qend") = py::none(), py::arg("check_values") = false);
   mod.def("rope_inplace", &rope_inplace);
+  mod.def("rope_inplace_one", &rope_inplace_one);
   mod.def("rms_norm_fwd", &rms_norm_fwd);
   mod.def("rms_norm_bwd", &rms_norm_bwd);
   mod.def("residual_rms_norm_fwd", &residual_rms_norm_fwd);

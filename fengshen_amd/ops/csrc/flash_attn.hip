@@ -1109,6 +1109,15 @@ __device__ __forceinline__ int v3_block_kstart_min(const int* ksb, int blk,
   return v3_wave_min(m);
 }
 
+// ---- grouped-query attention (GQA instantiations) --------------------------
+// K/V (and dK/dV) carry h_kv = h / G heads with FaStrides of their own (kvs,
+// gkvs); query head j uses KV head j / G.  fwd and dq keep one block per
+// query head and only point Kp/Vp at the shared head; dkv runs one block per
+// KV head and walks the G query heads of its group into one fp32
+// accumulator.  Like kstart, the arguments come last and are not read when
+// GQA = false, so the plain instantiations compile to the code they had.
+// Causal, no dropout, with or without KS.
+
 // delta[b,h,s] = rowsum(dO * O) over strided rows; same per-row arithmetic
 // as flash_delta_kernel.  Grid (x, h, b): blockIdx.y/z pick the head and
 // batch, so the [b, h, s] output index needs no division; the 4 waves of a
@@ -1138,7 +1147,8 @@ void flash_delta_v3_kernel(const bf16_t* __restrict__ dO,
   }
 }
 
-template <int D, bool CAUSAL, bool HAS_DROP, bool KS = false>
+template <int D, bool CAUSAL, bool HAS_DROP, bool KS = false,
+          bool GQA = false>
 __global__ __launch_bounds__(FA_WAVES * 64)
 void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
                               const bf16_t* __restrict__ K,
@@ -1150,8 +1160,10 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
                               int b, int h, int s, float scale,
                               unsigned int drop_thresh, float keep_scale,
                               unsigned long long drop_seed,
-                              const int* __restrict__ kstart) {
+                              const int* __restrict__ kstart,
+                              FaStrides kvs, int G) {
   static_assert(!KS || (CAUSAL && !HAS_DROP), "kstart: causal, no dropout");
+  static_assert(!GQA || (CAUSAL && !HAS_DROP), "GQA: causal, no dropout");
   constexpr int NC = D / 16;     // MFMA K=16 chunks
   constexpr int NTO = D / 32;    // 32-wide output d-tiles
   constexpr int SWB = fa_swb(D);
@@ -1173,8 +1185,12 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
   const long bh = (long)blockIdx.z * h + blockIdx.y;
   const long qoff = blockIdx.z * qs.b + blockIdx.y * qs.h;
   const bf16_t* Qp = Q + qoff;
-  const bf16_t* Kp = K + qoff;
-  const bf16_t* Vp = V + qoff;
+  // GQA: query head j reads KV head j / G through K/V's own strides
+  const long kvoff =
+      GQA ? blockIdx.z * kvs.b + (blockIdx.y / G) * kvs.h : qoff;
+  const long kv_r = GQA ? kvs.r : qs.r;
+  const bf16_t* Kp = K + kvoff;
+  const bf16_t* Vp = V + kvoff;
   bf16_t* Op = O + blockIdx.z * os.b + blockIdx.y * os.h;
 
   const int klen = CAUSAL ? s : min(klens ? klens[blockIdx.z] : s, s);
@@ -1244,8 +1260,8 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
       const long kr = KS ? min(kt0 * V3_KVBLK + i / D, s - 1)
                          : min(i / D, s - 1);
       const int kc = i % D;
-      k_reg[sweep] = *reinterpret_cast<const bf16x8*>(Kp + kr * qs.r + kc);
-      v_reg[sweep] = *reinterpret_cast<const bf16x8*>(Vp + kr * qs.r + kc);
+      k_reg[sweep] = *reinterpret_cast<const bf16x8*>(Kp + kr * kv_r + kc);
+      v_reg[sweep] = *reinterpret_cast<const bf16x8*>(Vp + kr * kv_r + kc);
     }
   }
 
@@ -1285,8 +1301,8 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
         if (i < ELEMS) {
           const long kr = min((long)(nb + i / D), (long)s - 1);
           const int kc = i % D;
-          k_reg[sweep] = *reinterpret_cast<const bf16x8*>(Kp + kr * qs.r + kc);
-          v_reg[sweep] = *reinterpret_cast<const bf16x8*>(Vp + kr * qs.r + kc);
+          k_reg[sweep] = *reinterpret_cast<const bf16x8*>(Kp + kr * kv_r + kc);
+          v_reg[sweep] = *reinterpret_cast<const bf16x8*>(Vp + kr * kv_r + kc);
         }
       }
     }
@@ -1474,7 +1490,7 @@ extern "C" void fs_flash_attn_fwd_v3_strided(
     (flash_attn_fwd_v3_kernel<DD, CC, DR>), \
     grid, block, 0, stream, (const bf16_t*)q, (const bf16_t*)k, \
     (const bf16_t*)v, (bf16_t*)o, lse, klens, qs, os, b, h, s, scale, dth, \
-    ksc, seed, (const int*)nullptr)
+    ksc, seed, (const int*)nullptr, FaStrides{}, 1)
   if (dth) {
     if (d == 128 && causal) V3F(128, true, true);
     else if (d == 128) V3F(128, false, true);
@@ -1507,11 +1523,40 @@ extern "C" void fs_flash_attn_fwd_v3_kstart(
     (flash_attn_fwd_v3_kernel<DD, true, false, true>), \
     grid, block, 0, stream, (const bf16_t*)q, (const bf16_t*)k, \
     (const bf16_t*)v, (bf16_t*)o, lse, (const int*)nullptr, qs, os, b, h, s, \
-    scale, 0u, 1.f, 0ull, kstart)
+    scale, 0u, 1.f, 0ull, kstart, FaStrides{}, 1)
   if (d == 128) V3K(128);
   else if (d == 96) V3K(96);
   else V3K(64);
 #undef V3K
+}
+
+// Grouped-query causal forward: q/o have h heads, k/v h_kv = h / G heads
+// with strides kvs3 of their own; query head j reads KV head j / G.
+// kstart may be null.  No dropout, no klens.
+extern "C" void fs_flash_attn_fwd_v3_gqa(
+    const void* q, const void* k, const void* v, void* o, float* lse,
+    const int* kstart, const long* qs3, const long* kvs3, const long* os3,
+    int b, int h, int h_kv, int s, int d, float scale, hipStream_t stream) {
+  const FaStrides qs{qs3[0], qs3[1], qs3[2]};
+  const FaStrides kvs{kvs3[0], kvs3[1], kvs3[2]};
+  const FaStrides os{os3[0], os3[1], os3[2]};
+  dim3 grid((s + V3_QBLK - 1) / V3_QBLK, h, b);
+  dim3 block(FA_WAVES * 64);
+#define V3G(DD, KK) hipLaunchKernelGGL( \
+    (flash_attn_fwd_v3_kernel<DD, true, false, KK, true>), \
+    grid, block, 0, stream, (const bf16_t*)q, (const bf16_t*)k, \
+    (const bf16_t*)v, (bf16_t*)o, lse, (const int*)nullptr, qs, os, b, h, s, \
+    scale, 0u, 1.f, 0ull, kstart, kvs, h / h_kv)
+  if (kstart) {
+    if (d == 128) V3G(128, true);
+    else if (d == 96) V3G(96, true);
+    else V3G(64, true);
+  } else {
+    if (d == 128) V3G(128, false);
+    else if (d == 96) V3G(96, false);
+    else V3G(64, false);
+  }
+#undef V3G
 }
 
 extern "C" void fs_flash_attn_fwd_v3(const void* q, const void* k,
@@ -1536,7 +1581,8 @@ extern "C" void fs_flash_attn_fwd_v3(const void* q, const void* k,
 #define B3_FB 32  // streamed tile width
 
 // q-major: wave owns 32 q rows (block 256), streams KV in 32-tiles.
-template <int D, bool CAUSAL, bool HAS_DROP, bool KS = false>
+template <int D, bool CAUSAL, bool HAS_DROP, bool KS = false,
+          bool GQA = false>
 __global__ __launch_bounds__(FA_WAVES * 64)
 void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
                                  const bf16_t* __restrict__ K,
@@ -1550,8 +1596,10 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
                                  int b, int h, int s, float scale,
                                  unsigned int drop_thresh, float keep_scale,
                                  unsigned long long drop_seed,
-                                 const int* __restrict__ kstart) {
+                                 const int* __restrict__ kstart,
+                                 FaStrides kvs, int G) {
   static_assert(!KS || (CAUSAL && !HAS_DROP), "kstart: causal, no dropout");
+  static_assert(!GQA || (CAUSAL && !HAS_DROP), "GQA: causal, no dropout");
   constexpr int NC = D / 16;
   constexpr int NTO = D / 32;
   constexpr int SWB = fa_swb(D);
@@ -1570,8 +1618,12 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
   const long bh = (long)blockIdx.z * h + blockIdx.y;
   const long qoff = blockIdx.z * qs.b + blockIdx.y * qs.h;
   const bf16_t* Qp = Q + qoff;
-  const bf16_t* Kp = K + qoff;
-  const bf16_t* Vp = V + qoff;
+  // GQA: query head j reads KV head j / G through K/V's own strides
+  const long kvoff =
+      GQA ? blockIdx.z * kvs.b + (blockIdx.y / G) * kvs.h : qoff;
+  const long kv_r = GQA ? kvs.r : qs.r;
+  const bf16_t* Kp = K + kvoff;
+  const bf16_t* Vp = V + kvoff;
   const bf16_t* dOp = dO + blockIdx.z * dos.b + blockIdx.y * dos.h;
   bf16_t* dQp = dQ + blockIdx.z * gs.b + blockIdx.y * gs.h;
   const float* lse = LSE + bh * s;
@@ -1635,8 +1687,8 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
   bf16x8 k_reg, v_reg;
   {
     const long krg = KS ? min(kt0 * B3_FB + st_r, s - 1) : min(st_r, s - 1);
-    k_reg = *reinterpret_cast<const bf16x8*>(Kp + krg * qs.r + st_c);
-    v_reg = *reinterpret_cast<const bf16x8*>(Vp + krg * qs.r + st_c);
+    k_reg = *reinterpret_cast<const bf16x8*>(Kp + krg * kv_r + st_c);
+    v_reg = *reinterpret_cast<const bf16x8*>(Vp + krg * kv_r + st_c);
   }
   if (st_on) {
     *reinterpret_cast<bf16x8*>(k_raw[0] + st_off) = k_reg;
@@ -1656,8 +1708,8 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
     __syncthreads();  // publishes buf[cur]; everyone done with buf[cur^1]
     if (kt + 1 < n_kv_tiles) {
       const long krg = min(k_base + B3_FB + st_r, s - 1);
-      k_reg = *reinterpret_cast<const bf16x8*>(Kp + krg * qs.r + st_c);
-      v_reg = *reinterpret_cast<const bf16x8*>(Vp + krg * qs.r + st_c);
+      k_reg = *reinterpret_cast<const bf16x8*>(Kp + krg * kv_r + st_c);
+      v_reg = *reinterpret_cast<const bf16x8*>(Vp + krg * kv_r + st_c);
     }
 
     if ((!CAUSAL || k_base <= q_last_w) && (!KS || k_base + B3_FB > ks_w)) {
@@ -1754,7 +1806,8 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
 // with kstart[i] <= the tile's last key (kstart is non-decreasing, so the
 // wrapper finds it with a searchsorted); the block takes the largest of
 // its four tiles' entries, clamped into [the block's first row, s - 1].
-template <int D, bool CAUSAL, bool HAS_DROP, bool KS = false>
+template <int D, bool CAUSAL, bool HAS_DROP, bool KS = false,
+          bool GQA = false>
 __global__ __launch_bounds__(FA_WAVES * 64)
 void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
                                   const bf16_t* __restrict__ K,
@@ -1770,8 +1823,10 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
                                   unsigned int drop_thresh, float keep_scale,
                                   unsigned long long drop_seed,
                                   const int* __restrict__ kstart,
-                                  const int* __restrict__ qend) {
+                                  const int* __restrict__ qend,
+                                  FaStrides kvs, FaStrides gkvs, int G) {
   static_assert(!KS || (CAUSAL && !HAS_DROP), "kstart: causal, no dropout");
+  static_assert(!GQA || (CAUSAL && !HAS_DROP), "GQA: causal, no dropout");
   constexpr int NC = D / 16;
   constexpr int NTO = D / 32;
   constexpr int SWB = fa_swb(D);
@@ -1794,13 +1849,20 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
   const int wave = threadIdx.x >> 6;
   const int hi = lane >> 5;
   const int ln = lane & 31;
-  const long bh = (long)blockIdx.z * h + blockIdx.y;
-  const long qoff = blockIdx.z * qs.b + blockIdx.y * qs.h;
+  // GQA: blockIdx.y is the KV head; the block walks the G query heads
+  // qh0 .. qh0 + G - 1 that share it (h stays the number of query heads)
+  const unsigned int qh0 = GQA ? blockIdx.y * G : blockIdx.y;
+  const long bh = (long)blockIdx.z * h + qh0;
+  const long qoff = blockIdx.z * qs.b + qh0 * qs.h;
   const bf16_t* Qp = Q + qoff;
-  const bf16_t* Kp = K + qoff;
-  const bf16_t* Vp = V + qoff;
-  const bf16_t* dOp = dO + blockIdx.z * dos.b + blockIdx.y * dos.h;
-  const long goff = blockIdx.z * gs.b + blockIdx.y * gs.h;
+  const long kvoff = GQA ? blockIdx.z * kvs.b + blockIdx.y * kvs.h : qoff;
+  const long kv_r = GQA ? kvs.r : qs.r;
+  const bf16_t* Kp = K + kvoff;
+  const bf16_t* Vp = V + kvoff;
+  const bf16_t* dOp = dO + blockIdx.z * dos.b + qh0 * dos.h;
+  const long goff = GQA ? blockIdx.z * gkvs.b + blockIdx.y * gkvs.h
+                        : blockIdx.z * gs.b + blockIdx.y * gs.h;
+  const long g_r = GQA ? gkvs.r : gs.r;
   bf16_t* dKp = dK + goff;
   bf16_t* dVp = dV + goff;
   const float* lse = LSE + bh * s;
@@ -1866,11 +1928,18 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     k_frag[c] = *reinterpret_cast<const bf16x8*>(
-        Kp + (long)my_kv * qs.r + c * 16 + hi * 8);
+        Kp + (long)my_kv * kv_r + c * 16 + hi * 8);
     v_frag[c] = *reinterpret_cast<const bf16x8*>(
-        Vp + (long)my_kv * qs.r + c * 16 + hi * 8);
+        Vp + (long)my_kv * kv_r + c * 16 + hi * 8);
   }
 
+  // GQA: one pass over the query tiles per query head of the group, all
+  // into the same fp32 dk_acc / dv_acc (one rounding at the end, one owner
+  // per dK/dV row).  kstart / qend are per batch row, so the bounds hold
+  // for every member.  The group loop is folded into the tile loop (its
+  // last tile rewinds qt and steps the per-head bases), so the plain
+  // instantiations keep the single loop, and the code, they had before.
+  int gm = 0;
   for (int qt = first_qt; qt < n_q_tiles; ++qt) {
     const int q_base = qt * B3_FB;
     __syncthreads();
@@ -1972,6 +2041,14 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
             pa, bfrag, dk_acc[t], 0, 0, 0);
       }
     }
+    if (GQA && qt + 1 == n_q_tiles && ++gm < G) {
+      // next query head of the group
+      qt = first_qt - 1;
+      Qp += qs.h;
+      dOp += dos.h;
+      lse += s;
+      dlt += s;
+    }
   }
 
   if (!kv_active) return;
@@ -1980,8 +2057,8 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
     const int kvrow = kv0w + (r & 3) + 8 * (r >> 2) + 4 * hi;
 #pragma unroll
     for (int t = 0; t < NTO; ++t) {
-      dKp[(long)kvrow * gs.r + t * 32 + ln] = __float2bfloat16(dk_acc[t][r]);
-      dVp[(long)kvrow * gs.r + t * 32 + ln] = __float2bfloat16(dv_acc[t][r]);
+      dKp[(long)kvrow * g_r + t * 32 + ln] = __float2bfloat16(dk_acc[t][r]);
+      dVp[(long)kvrow * g_r + t * 32 + ln] = __float2bfloat16(dv_acc[t][r]);
     }
   }
 }
@@ -2011,12 +2088,45 @@ static void launch_bwd_v3(const void* q, const void* k, const void* v,
                      grid, block, 0, stream, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout,
                      lse, delta_ws, (bf16_t*)dq, klens, qs, dos, gs, b, h, s,
-                     scale, dth, ksc, seed, kstart);
+                     scale, dth, ksc, seed, kstart, FaStrides{}, 1);
   hipLaunchKernelGGL((flash_attn_bwd_dkv_v3_kernel<D, CAUSAL, HAS_DROP, KS>),
                      grid, block, 0, stream, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout,
                      lse, delta_ws, (bf16_t*)dk, (bf16_t*)dv, klens, qs, dos,
-                     gs, b, h, s, scale, dth, ksc, seed, kstart, qend);
+                     gs, b, h, s, scale, dth, ksc, seed, kstart, qend,
+                     FaStrides{}, FaStrides{}, 1);
+}
+
+// Grouped-query backward: delta and dq run per query head (grid y = h), dkv
+// per KV head (grid y = h_kv) with the group loop inside the block.
+template <int D, bool KS>
+static void launch_bwd_v3_gqa(const void* q, const void* k, const void* v,
+                              const void* o, const void* dout,
+                              const float* lse, void* dq, void* dk, void* dv,
+                              float* delta_ws, FaStrides qs, FaStrides kvs,
+                              FaStrides os, FaStrides dos, FaStrides gs,
+                              FaStrides gkvs, int b, int h, int h_kv, int s,
+                              float scale, hipStream_t stream,
+                              const int* kstart, const int* qend) {
+  int bx = (s + 31) / 32;
+  if (bx > 16) bx = 16;
+  hipLaunchKernelGGL((flash_delta_v3_kernel<D>), dim3(bx, h, b), dim3(256),
+                     0, stream, (const bf16_t*)dout, (const bf16_t*)o,
+                     delta_ws, dos, os, h, s);
+  const int G = h / h_kv;
+  const int nx = (s + V3_QBLK - 1) / V3_QBLK;
+  dim3 block(FA_WAVES * 64);
+  hipLaunchKernelGGL(
+      (flash_attn_bwd_dq_v3_kernel<D, true, false, KS, true>), dim3(nx, h, b),
+      block, 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
+      (const bf16_t*)dout, lse, delta_ws, (bf16_t*)dq, (const int*)nullptr,
+      qs, dos, gs, b, h, s, scale, 0u, 1.f, 0ull, kstart, kvs, G);
+  hipLaunchKernelGGL(
+      (flash_attn_bwd_dkv_v3_kernel<D, true, false, KS, true>),
+      dim3(nx, h_kv, b), block, 0, stream, (const bf16_t*)q, (const bf16_t*)k,
+      (const bf16_t*)v, (const bf16_t*)dout, lse, delta_ws, (bf16_t*)dk,
+      (bf16_t*)dv, (const int*)nullptr, qs, dos, gs, b, h, s, scale, 0u, 1.f,
+      0ull, kstart, qend, kvs, gkvs, G);
 }
 
 // qs3: q|k|v, os3: o, dos3: dout, gs3: dq|dk|dv (batch, head, row) strides.
@@ -2075,6 +2185,35 @@ extern "C" void fs_flash_attn_bwd_v3_kstart(
   else if (d == 96) BWD3K(96);
   else BWD3K(64);
 #undef BWD3K
+}
+
+// kvs3: k|v, gkvs3: dk|dv strides; kstart / qend both null or both set.
+extern "C" void fs_flash_attn_bwd_v3_gqa(
+    const void* q, const void* k, const void* v, const void* o,
+    const void* dout, const float* lse, void* dq, void* dk, void* dv,
+    float* delta_ws, const int* kstart, const int* qend, const long* qs3,
+    const long* kvs3, const long* os3, const long* dos3, const long* gs3,
+    const long* gkvs3, int b, int h, int h_kv, int s, int d, float scale,
+    hipStream_t stream) {
+  const FaStrides qs{qs3[0], qs3[1], qs3[2]};
+  const FaStrides kvs{kvs3[0], kvs3[1], kvs3[2]};
+  const FaStrides os{os3[0], os3[1], os3[2]};
+  const FaStrides dos{dos3[0], dos3[1], dos3[2]};
+  const FaStrides gs{gs3[0], gs3[1], gs3[2]};
+  const FaStrides gkvs{gkvs3[0], gkvs3[1], gkvs3[2]};
+#define BWD3G(DD, KK) launch_bwd_v3_gqa<DD, KK>( \
+      q, k, v, o, dout, lse, dq, dk, dv, delta_ws, qs, kvs, os, dos, gs, \
+      gkvs, b, h, h_kv, s, scale, stream, kstart, qend)
+  if (kstart) {
+    if (d == 128) BWD3G(128, true);
+    else if (d == 96) BWD3G(96, true);
+    else BWD3G(64, true);
+  } else {
+    if (d == 128) BWD3G(128, false);
+    else if (d == 96) BWD3G(96, false);
+    else BWD3G(64, false);
+  }
+#undef BWD3G
 }
 
 extern "C" void fs_flash_attn_bwd_v3(const void* q, const void* k,

@@ -391,17 +391,20 @@ __global__ void rope_kernel(const T* __restrict__ x, T* __restrict__ out,
 // rotated where they lie.  Each thread reads both halves of its pairs
 // before it writes either, and no pair is shared between threads.  Pairs
 // are walked in (tensor, b, s, head, d) order — memory order of the packed
-// layout.  Same fp32 math and rounding as rope_kernel.
+// layout.  Same fp32 math and rounding as rope_kernel.  `total` is the number
+// of pairs to rotate: 2 * pairs_per_tensor, or pairs_per_tensor to rotate xq
+// alone (grouped-query layouts, where the q and k heads of the packed buffer
+// form one [b, h + h_kv, s, hn] view).
 template <typename T, bool BWD>
 __global__ void rope_inplace_kernel(T* __restrict__ xq, T* __restrict__ xk,
                                     const float* __restrict__ cos_t,
                                     const float* __restrict__ sin_t,
-                                    long pairs_per_tensor, int np, int s,
-                                    int h2, int offset, long sb, long sh,
-                                    long sr) {
+                                    long pairs_per_tensor, long total,
+                                    int np, int s, int h2, int offset,
+                                    long sb, long sh, long sr) {
   const long stride = (long)gridDim.x * blockDim.x * 8;
   for (long i0 = (long)(blockIdx.x * blockDim.x + threadIdx.x) * 8;
-       i0 < 2 * pairs_per_tensor; i0 += stride) {
+       i0 < total; i0 += stride) {
     T* x = i0 < pairs_per_tensor ? xq : xk;
     const long i = i0 < pairs_per_tensor ? i0 : i0 - pairs_per_tensor;
     const long d = i % h2;
@@ -844,22 +847,24 @@ void fs_rope(const void* x, void* out, const float* cos_t, const float* sin_t,
   });
 }
 
+// xk == nullptr: rotate xq alone.
 void fs_rope_inplace(void* xq, void* xk, const float* cos_t,
                      const float* sin_t, int b, int np, int seq, int hn,
                      long sb, long sh, long sr, int offset, int bwd,
                      int dtype, hipStream_t s) {
   const int h2 = hn / 2;
   const long per_tensor = (long)b * np * seq * h2;
-  int grid = grid_for(2 * per_tensor / 8);
+  const long total = xk ? 2 * per_tensor : per_tensor;
+  int grid = grid_for(total / 8);
   DISPATCH_DTYPE(dtype, T, {
     if (bwd)
       hipLaunchKernelGGL((rope_inplace_kernel<T, true>), dim3(grid),
                          dim3(256), 0, s, (T*)xq, (T*)xk, cos_t, sin_t,
-                         per_tensor, np, seq, h2, offset, sb, sh, sr);
+                         per_tensor, total, np, seq, h2, offset, sb, sh, sr);
     else
       hipLaunchKernelGGL((rope_inplace_kernel<T, false>), dim3(grid),
                          dim3(256), 0, s, (T*)xq, (T*)xk, cos_t, sin_t,
-                         per_tensor, np, seq, h2, offset, sb, sh, sr);
+                         per_tensor, total, np, seq, h2, offset, sb, sh, sr);
   });
 }
 
@@ -1088,11 +1093,19 @@ extern "C" void fs_bf16_gemv(const void* w, const void* x, void* y, int batch,
 // over the cache prefix [0..pos] -> context vector.  The eager tail
 // (rotate-half cats, fp32 casts of the cache, index_copy, softmax) was
 // ~40% of the 13B per-token time (profiles/decprof).
-//   qkv    [b, 3*H]     H = nh*D, straight out of the fused qkv GEMV
-//   kc/vc  [b, nh, L, D] static caches, row `pos` written here
+//   qkv    [b, (nh + 2*nkv)*D]  [q | k | v] straight out of the fused qkv
+//          GEMV; nh query heads, nkv KV heads (nkv == nh: plain MHA)
+//   kc/vc  [b, nkv, L, D] static caches, row `pos` written here
 //   cos/sin [max_len, D] fp32 rope tables; pos = device scalar (long)
-//   ctx    [b, H]
-// Grid (b*nh) x 128 threads.  K tiles staged in LDS as fp32 rows padded
+//   ctx    [b, H]               H = nh*D
+// Grid (b*nh) x 128 threads.  Grouped queries (nkv < nh): query head h reads
+// the cache of KV head h / G, G = nh / nkv.  Every block of a group computes
+// the same roped k row and holds the same v row, so none waits for another:
+// exactly one block per KV head (h % G == 0) writes row `pos` of the caches,
+// and NO block reads that row back from global memory — K at `pos` comes
+// from ks_new in LDS, V at `pos` from the thread's own v_new register.  (A
+// block reading the row while a sibling writes it would be a race.)
+// The G blocks of a group re-read the same K/V rows through L2.  K tiles staged in LDS as fp32 rows padded
 // to D+1 (bank-conflict-free per-thread row reads); V read coalesced by
 // the D lanes in the accumulate phase.
 
@@ -1106,12 +1119,15 @@ void decode_attn_kernel(const bf16_t* __restrict__ qkv,
                         const float* __restrict__ sin_t,
                         const long* __restrict__ pos_p,
                         bf16_t* __restrict__ ctx,
-                        int nh, int cache_len, float scale) {
+                        int nh, int nkv, int cache_len, float scale) {
   const int tid = threadIdx.x;
   const int bh = blockIdx.x;  // b*nh + h
   const int b = bh / nh, h = bh % nh;
+  const int G = nh / nkv;
+  const int kvh = h / G;
   const int pos = (int)pos_p[0];
   const int H = nh * D;
+  const long W = (long)(nh + 2 * nkv) * D;  // qkv row
 
   __shared__ float qraw[D], kraw[D];
   __shared__ float qs[D], ks_new[D];
@@ -1122,9 +1138,9 @@ void decode_attn_kernel(const bf16_t* __restrict__ qkv,
   // ---- phase 0: rope q/k at pos, write the cache row -------------------
   float v_new = 0.f;
   if (tid < D) {
-    qraw[tid] = to_f32<bf16_t>(qkv[(long)b * 3 * H + h * D + tid]);
-    kraw[tid] = to_f32<bf16_t>(qkv[(long)b * 3 * H + H + h * D + tid]);
-    v_new = to_f32<bf16_t>(qkv[(long)b * 3 * H + 2 * H + h * D + tid]);
+    qraw[tid] = to_f32<bf16_t>(qkv[b * W + h * D + tid]);
+    kraw[tid] = to_f32<bf16_t>(qkv[b * W + H + kvh * D + tid]);
+    v_new = to_f32<bf16_t>(qkv[b * W + H + (nkv + kvh) * D + tid]);
   }
   __syncthreads();
   if (tid < D) {
@@ -1139,30 +1155,30 @@ void decode_attn_kernel(const bf16_t* __restrict__ qkv,
     }
     qs[tid] = q * scale;
     ks_new[tid] = k;
-    const long coff = (((long)b * nh + h) * cache_len + pos) * D + tid;
-    kc[coff] = from_f32<bf16_t>(k);
-    vc[coff] = from_f32<bf16_t>(v_new);
+    if (h % G == 0) {  // the group's one writer
+      const long coff = (((long)b * nkv + kvh) * cache_len + pos) * D + tid;
+      kc[coff] = from_f32<bf16_t>(k);
+      vc[coff] = from_f32<bf16_t>(v_new);
+    }
   }
-  // make the cache row visible to this block's phase-2 V reads
-  __threadfence();
   __syncthreads();
 
   // ---- phases 1+2: online softmax over chunks of 128 positions ---------
-  const bf16_t* kbase = kc + ((long)b * nh + h) * (long)cache_len * D;
-  const bf16_t* vbase = vc + ((long)b * nh + h) * (long)cache_len * D;
+  const bf16_t* kbase = kc + ((long)b * nkv + kvh) * (long)cache_len * D;
+  const bf16_t* vbase = vc + ((long)b * nkv + kvh) * (long)cache_len * D;
   float m_run = -INFINITY, l_run = 0.f, oacc = 0.f;
   for (int p0 = 0; p0 <= pos; p0 += FS_DEC_BLK) {
     const int nrow = min(FS_DEC_BLK, pos + 1 - p0);
     // stage K rows [p0, p0+nrow) -> fp32 LDS (coalesced 16B global loads)
     for (int idx = tid * 8; idx < nrow * D; idx += FS_DEC_BLK * 8) {
       const int r = idx / D, c = idx % D;  // D % 8 == 0: no row straddle
+      if (p0 + r == pos) continue;  // this step's row: from ks_new below
       float kv[8];
       load8<bf16_t>(kbase + (long)(p0 + r) * D + c, kv);
 #pragma unroll
       for (int j = 0; j < 8; ++j) ktile[r][c + j] = kv[j];
     }
-    __syncthreads();
-    // the row written this step comes from LDS (no coherence question)
+    // the row of this step comes from LDS, never from the cache
     if (pos >= p0 && pos < p0 + FS_DEC_BLK && tid < D)
       ktile[pos - p0][tid] = ks_new[tid];
     __syncthreads();
@@ -1189,8 +1205,12 @@ void decode_attn_kernel(const bf16_t* __restrict__ qkv,
     // context accumulate: thread tid < D owns ctx element tid
     if (tid < D) {
       float acc = oacc * alpha;
-      for (int t = 0; t < nrow; ++t)
+      // row `pos` is always the chunk's last one; its V is v_new (bf16 in
+      // qkv, so the value the cache row holds), added in the same order
+      const int ncache = min(nrow, pos - p0);
+      for (int t = 0; t < ncache; ++t)
         acc += pbuf[t] * to_f32<bf16_t>(vbase[(long)(p0 + t) * D + tid]);
+      if (ncache < nrow) acc += pbuf[ncache] * v_new;
       oacc = acc;
     }
     __syncthreads();  // pbuf/ktile reuse in next chunk
@@ -1202,22 +1222,22 @@ void decode_attn_kernel(const bf16_t* __restrict__ qkv,
 extern "C" void fs_decode_attn(const void* qkv, void* kc, void* vc,
                                const float* cos_t, const float* sin_t,
                                const void* pos, void* ctx, int b, int nh,
-                               int d, int cache_len, float scale, int rope,
-                               hipStream_t s) {
+                               int nkv, int d, int cache_len, float scale,
+                               int rope, hipStream_t s) {
 #define FS_DEC_CASE(D)                                                       \
   if (d == D) {                                                              \
     if (rope)                                                                \
       hipLaunchKernelGGL((decode_attn_kernel<D, true>), dim3(b * nh),        \
                          dim3(FS_DEC_BLK), 0, s, (const bf16_t*)qkv,         \
                          (bf16_t*)kc, (bf16_t*)vc, cos_t, sin_t,             \
-                         (const long*)pos, (bf16_t*)ctx, nh, cache_len,      \
-                         scale);                                             \
+                         (const long*)pos, (bf16_t*)ctx, nh, nkv,            \
+                         cache_len, scale);                                  \
     else                                                                     \
       hipLaunchKernelGGL((decode_attn_kernel<D, false>), dim3(b * nh),       \
                          dim3(FS_DEC_BLK), 0, s, (const bf16_t*)qkv,         \
                          (bf16_t*)kc, (bf16_t*)vc, cos_t, sin_t,             \
-                         (const long*)pos, (bf16_t*)ctx, nh, cache_len,      \
-                         scale);                                             \
+                         (const long*)pos, (bf16_t*)ctx, nh, nkv,            \
+                         cache_len, scale);                                  \
     return;                                                                  \
   }
   FS_DEC_CASE(64)

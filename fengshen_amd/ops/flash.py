@@ -12,7 +12,11 @@ generality (ref flash_attention.py:174 call semantics):
   keys kstart[i] <= j <= i) for padded and packed batches: right padding
   (0), left padding by p (p), packed documents (start of the row's
   document); a pad row sees only itself (kstart[i] = i).  v3 shapes only,
-  no dropout.
+  no dropout;
+- grouped-query attention: k/v with h_kv heads, h % h_kv == 0, query head
+  j uses KV head j // (h / h_kv) (HF ``repeat_kv`` order).  Native in the
+  causal v3 kernels without dropout, with or without ``kstart``; K/V are
+  never expanded and dK/dV come back with h_kv heads.
 """
 from __future__ import annotations
 
@@ -43,6 +47,36 @@ def _v3_eligible(ext, q, k, causal, klens, dropout_p):
         return os.environ.get("FENGSHEN_FLASH_V3_DROP") == "1" \
             and q.shape[-1] in (64, 96)
     return True
+
+
+def gqa_flash_enabled() -> bool:
+    """FENGSHEN_GQA_FLASH=0 expands K/V to the query heads in front of
+    every attention path instead of using the grouped-query kernels."""
+    return os.environ.get("FENGSHEN_GQA_FLASH", "1") != "0"
+
+
+def gqa_flash_supported(q: torch.Tensor, k: torch.Tensor, causal: bool,
+                        dropout_p: float) -> bool:
+    """Calls the grouped-query kernels cover: bf16 on the GPU, causal
+    self-attention at v3 shapes, no dropout (a mask must reduce to kstart —
+    the caller's check)."""
+    return (gqa_flash_enabled() and causal and q.is_cuda
+            and q.shape[1] % k.shape[1] == 0
+            and kstart_supported(q.shape[-1], q.shape[-2], k.shape[-2],
+                                 q.dtype, dropout_p))
+
+
+def expand_kv(x: torch.Tensor, num_heads: int) -> torch.Tensor:
+    """[b, h_kv, s, d] -> [b, h, s, d], query head j <- KV head j // G.
+    Autograd sums the group's gradients."""
+    b, h_kv, s, d = x.shape
+    if h_kv == num_heads:
+        return x
+    if num_heads % h_kv:
+        raise ValueError(f"{num_heads} query heads are not a multiple of "
+                         f"{h_kv} KV heads")
+    g = num_heads // h_kv
+    return x[:, :, None].expand(b, h_kv, g, s, d).reshape(b, num_heads, s, d)
 
 
 def varlen_flash_enabled() -> bool:
@@ -163,7 +197,10 @@ class _FlashAttention(torch.autograd.Function):
             o, lse = ext.flash_attn_fwd_v3(q, k, v, scale, causal, klens,
                                            dropout_p, seed, kstart=kstart)
             ctx.qend = kstart_qend(kstart)
-        elif _v3_eligible(ext, q, k, causal, klens, dropout_p):
+        elif k.shape[1] != q.shape[1] \
+                or _v3_eligible(ext, q, k, causal, klens, dropout_p):
+            # grouped-query K/V exist in the v3 kernels only; the binding
+            # raises on what they do not cover
             o, lse = ext.flash_attn_fwd_v3(q, k, v, scale, causal, klens,
                                            dropout_p, seed)
         else:
@@ -186,7 +223,9 @@ class _FlashAttention(torch.autograd.Function):
                 q, k, v, o, do.contiguous(), lse, ctx.scale, ctx.causal,
                 ctx.klens, ctx.dropout_p, ctx.seed, kstart=ctx.kstart,
                 qend=ctx.qend)
-        elif _v3_eligible(ext, q, k, ctx.causal, ctx.klens, ctx.dropout_p):
+        elif k.shape[1] != q.shape[1] \
+                or _v3_eligible(ext, q, k, ctx.causal, ctx.klens,
+                                ctx.dropout_p):
             dq, dk, dv = ext.flash_attn_bwd_v3(
                 q, k, v, o, do.contiguous(), lse, ctx.scale, ctx.causal,
                 ctx.klens, ctx.dropout_p, ctx.seed)
@@ -197,15 +236,33 @@ class _FlashAttention(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None, None, None
 
 
-def _thirds(qkv, num_heads):
-    """[b, s, >=3*np*hn] packed buffer -> q, k, v as [b, np, s, hn] views."""
-    h = qkv.shape[-1] // 3
-    return tuple(qkv.narrow(2, i * h, h).unflatten(2, (num_heads, -1))
-                 .transpose(1, 2) for i in range(3))
+def _split_qkv(qkv, num_heads, num_kv_heads):
+    """[b, s, (np + 2*nkv)*hn] packed buffer, laid out [q | k | v] -> q as a
+    [b, np, s, hn] view and k, v as [b, nkv, s, hn] views."""
+    hn = qkv.shape[-1] // (num_heads + 2 * num_kv_heads)
+    wq, wkv = num_heads * hn, num_kv_heads * hn
+    q = qkv.narrow(2, 0, wq).unflatten(2, (num_heads, hn)).transpose(1, 2)
+    k, v = (qkv.narrow(2, wq + i * wkv, wkv).unflatten(2, (num_kv_heads, hn))
+            .transpose(1, 2) for i in range(2))
+    return q, k, v
+
+
+def _rope_packed(qkv, num_heads, num_kv_heads, cos, sin, offset, bwd):
+    """Rotate the q and k heads of a packed buffer in place."""
+    if num_kv_heads == num_heads:
+        q, k, _ = _split_qkv(qkv, num_heads, num_kv_heads)
+        get_ext().rope_inplace(q, k, cos, sin, offset, bwd)
+        return
+    # q and k are adjacent and share the head stride: one
+    # [b, np + nkv, s, hn] view, one launch
+    n = num_heads + num_kv_heads
+    hn = qkv.shape[-1] // (n + num_kv_heads)
+    qk = qkv.narrow(2, 0, n * hn).unflatten(2, (n, hn)).transpose(1, 2)
+    get_ext().rope_inplace_one(qk, cos, sin, offset, bwd)
 
 
 class _RopePackedInplace(torch.autograd.Function):
-    """Rotates the q and k thirds of a packed [b, s, 3*np*hn] buffer in
+    """Rotates the q and k heads of a packed [b, s, (np + 2*nkv)*hn] buffer in
     place and returns it marked dirty, so autograd sees the overwrite (no
     linear backward needs its own output, so overwriting the projection
     output is sound).  A function of its own because autograd allows an
@@ -213,12 +270,13 @@ class _RopePackedInplace(torch.autograd.Function):
     in a Function with a single output."""
 
     @staticmethod
-    def forward(ctx, qkv, num_heads, cos, sin, offset):
-        q, k, _ = _thirds(qkv, num_heads)
-        get_ext().rope_inplace(q, k, cos, sin, offset, False)
+    def forward(ctx, qkv, num_heads, cos, sin, offset, num_kv_heads=None):
+        num_kv_heads = num_kv_heads or num_heads
+        _rope_packed(qkv, num_heads, num_kv_heads, cos, sin, offset, False)
         ctx.mark_dirty(qkv)
         ctx.save_for_backward(cos, sin)
         ctx.num_heads = num_heads
+        ctx.num_kv_heads = num_kv_heads
         ctx.offset = offset
         return qkv
 
@@ -232,22 +290,26 @@ class _RopePackedInplace(torch.autograd.Function):
         if grad.stride(-1) != 1 or any(st % 8 for st in grad.stride()[:-1]) \
                 or grad.storage_offset() % 8:
             grad = grad.contiguous()
-        dq, dk, _ = _thirds(grad, ctx.num_heads)
-        get_ext().rope_inplace(dq, dk, cos, sin, ctx.offset, True)
-        return grad, None, None, None, None
+        _rope_packed(grad, ctx.num_heads, ctx.num_kv_heads, cos, sin,
+                     ctx.offset, True)
+        return grad, None, None, None, None, None
 
 
 class _PackedFlash(torch.autograd.Function):
     """v3 flash attention straight on the packed QKV buffer: the strided
-    kernels read the three thirds where the GEMM left them and write O as
-    [b, s, np*hn]; backward writes dq/dk/dv into the thirds of one packed
-    gradient.  No layout copies, no ``cat``."""
+    kernels read the three parts where the GEMM left them and write O as
+    [b, s, np*hn]; backward writes dq/dk/dv into the parts of one packed
+    gradient.  No layout copies, no ``cat``.  With num_kv_heads < num_heads
+    the k and v parts are nkv*hn wide (grouped-query kernels)."""
 
     @staticmethod
-    def forward(ctx, qkv, num_heads, scale, causal, klens, kstart=None):
+    def forward(ctx, qkv, num_heads, scale, causal, klens, kstart=None,
+                num_kv_heads=None):
         b, s, w = qkv.shape
-        q, k, v = _thirds(qkv, num_heads)
-        o = torch.empty(b, s, w // 3, dtype=qkv.dtype, device=qkv.device)
+        nkv = num_kv_heads or num_heads
+        q, k, v = _split_qkv(qkv, num_heads, nkv)
+        o = torch.empty(b, s, w // (num_heads + 2 * nkv) * num_heads,
+                        dtype=qkv.dtype, device=qkv.device)
         ov = o.unflatten(2, (num_heads, -1)).transpose(1, 2)
         if kstart is not None:
             lse = get_ext().flash_attn_fwd_v3_strided(
@@ -259,6 +321,7 @@ class _PackedFlash(torch.autograd.Function):
         ctx.kstart = kstart
         ctx.save_for_backward(qkv, o, lse)
         ctx.num_heads = num_heads
+        ctx.num_kv_heads = nkv
         ctx.scale = scale
         ctx.causal = causal
         ctx.klens = klens
@@ -268,13 +331,13 @@ class _PackedFlash(torch.autograd.Function):
     def backward(ctx, do):
         qkv, o, lse = ctx.saved_tensors
         np_ = ctx.num_heads
-        q, k, v = _thirds(qkv, np_)
+        q, k, v = _split_qkv(qkv, np_, ctx.num_kv_heads)
         # dO is read where it lies as long as its last dim is contiguous
         if do.stride(-1) != 1 or any(st % 8 for st in do.stride()[:-1]) \
                 or do.storage_offset() % 8:
             do = do.contiguous()
         grad = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
-        dq, dk, dv = _thirds(grad, np_)
+        dq, dk, dv = _split_qkv(grad, np_, ctx.num_kv_heads)
         kw = {}
         if ctx.kstart is not None:
             kw = {"kstart": ctx.kstart, "qend": ctx.qend}
@@ -282,20 +345,25 @@ class _PackedFlash(torch.autograd.Function):
             q, k, v, o.unflatten(2, (np_, -1)).transpose(1, 2),
             do.unflatten(2, (np_, -1)).transpose(1, 2), lse, dq, dk, dv,
             ctx.scale, ctx.causal, ctx.klens, **kw)
-        return grad, None, None, None, None, None
+        return grad, None, None, None, None, None, None
 
 
 def packed_attn_eligible(qkv, head_dim: int, causal: bool, mask,
-                         dropout_p: float) -> bool:
-    """True when self-attention can run on the packed [b, s, 3*np*hn]
+                         dropout_p: float, num_heads: Optional[int] = None,
+                         num_kv_heads: Optional[int] = None) -> bool:
+    """True when self-attention can run on the packed [b, s, (np+2*nkv)*hn]
     projection output in place: v3 shapes (d in {64, 96, 128}, s % 64 == 0),
-    bf16, no dropout.  A mask must still reduce to klens (bidirectional)
+    bf16, no dropout.  Grouped-query layouts (num_kv_heads != num_heads)
+    are causal only and off under FENGSHEN_GQA_FLASH=0.  A mask must still reduce to klens (bidirectional)
     or to kstart (causal) — checked by the caller; under causal a mask is
     refused outright when FENGSHEN_VARLEN_FLASH=0.  FENGSHEN_PACKED_ATTN=0
     forces the chunk/transpose/contiguous path."""
     if os.environ.get("FENGSHEN_PACKED_ATTN", "1") == "0":
         return False
     if qkv.dtype != torch.bfloat16 or qkv.dim() != 3 or dropout_p > 0:
+        return False
+    if num_kv_heads is not None and num_kv_heads != num_heads \
+            and not (causal and gqa_flash_enabled()):
         return False
     s = qkv.shape[1]
     if head_dim not in (64, 96, 128) or s % 64 != 0 or s < 64:
@@ -311,17 +379,19 @@ def packed_self_attention(qkv: torch.Tensor, num_heads: int,
                           sin: Optional[torch.Tensor], offset: int,
                           scale: float, causal: bool = True,
                           klens: Optional[torch.Tensor] = None,
-                          kstart: Optional[torch.Tensor] = None
+                          kstart: Optional[torch.Tensor] = None,
+                          num_kv_heads: Optional[int] = None
                           ) -> torch.Tensor:
-    """qkv [b, s, 3*np*hn] bf16, partition-local layout [q | k | v], last dim
-    unit-stride.  Rotates q/k IN PLACE when cos/sin are given (pass None
+    """qkv [b, s, (np + 2*nkv)*hn] bf16 (nkv = num_kv_heads, default np),
+    partition-local layout [q | k | v], last dim unit-stride.  Rotates q/k IN PLACE when cos/sin are given (pass None
     for no rotary) and returns the context as [b, s, np*hn], ready for the
     output projection.  Callers must not reuse ``qkv`` afterwards.
     ``kstart`` (int32 [b, s], causal only): per-row key start."""
     if cos is not None:
-        qkv = _RopePackedInplace.apply(qkv, num_heads, cos, sin, offset)
+        qkv = _RopePackedInplace.apply(qkv, num_heads, cos, sin, offset,
+                                       num_kv_heads)
     return _PackedFlash.apply(qkv, num_heads, float(scale), causal, klens,
-                              kstart)
+                              kstart, num_kv_heads)
 
 
 def _draw_seed(device) -> int:
@@ -343,7 +413,9 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                     klens: Optional[torch.Tensor] = None,
                     dropout_p: float = 0.0,
                     kstart: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """q [b,h,sq,d], k/v [b,h,sk,d] bf16 contiguous.  dropout_p > 0
+    """q [b,h,sq,d], k/v [b,h_kv,sk,d] bf16 contiguous; h_kv < h (grouped
+    queries) needs causal v3 shapes without dropout and returns dk/dv with
+    h_kv heads — anything else raises.  dropout_p > 0
     applies attention dropout with an in-kernel counter hash (no mask
     tensor); the normalizer uses the undropped row sum, matching eager
     dropout(softmax(S)) @ V.  kstart (int32 [b, s], non-decreasing along

@@ -474,7 +474,15 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
               dropout_p: float = 0.0, training: bool = False,
               scale: Optional[float] = None,
               kstart: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """q,k,v: [b, np, s, hn] -> context [b, np, sq, hn].
+    """q: [b, np, sq, hn], k,v: [b, nkv, sk, hn] -> context [b, np, sq, hn].
+
+    nkv < np is grouped-query attention (np % nkv == 0, query head j uses
+    KV head j // (np / nkv)).  The grouped-query flash kernels take it when
+    they cover the call (GPU, bf16, causal with sq == sk, hn in {64, 96,
+    128}, s % 64 == 0, no active dropout, mask absent or reducible to
+    kstart); everything else, and everything under FENGSHEN_GQA_FLASH=0,
+    expands K/V to np heads and proceeds as for nkv == np, autograd summing
+    the group's gradients.
 
     GPU path: flash-style fused HIP kernel when available (csrc/flash_attn.hip)
     else hipBLASLt bmm + fused-softmax kernel.  CPU path: eager oracle.
@@ -492,6 +500,22 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     if kstart is not None and not (causal and sq == sk):
         raise ValueError("kstart needs causal self-attention (sq == sk)")
     ext = get_ext() if use_hip(q) else None
+    if k.shape[1] != np_:
+        from fengshen_amd.ops.flash import (
+            expand_kv, flash_attention, gqa_flash_supported, mask_to_kstart,
+            varlen_flash_enabled)
+        drop = dropout_p if training else 0.0
+        if ext is not None and hasattr(ext, "flash_attn_fwd_v3") \
+                and gqa_flash_supported(q, k, causal, drop):
+            ks = kstart
+            if (ks is not None or mask is not None) \
+                    and not varlen_flash_enabled():
+                ks = None
+            elif ks is None and mask is not None:
+                ks = mask_to_kstart(mask, sq)
+            if ks is not None or (mask is None and kstart is None):
+                return flash_attention(q, k, v, scale, causal=True, kstart=ks)
+        k, v = expand_kv(k, np_), expand_kv(v, np_)
     if ext is not None and hasattr(ext, "flash_attn_fwd"):
         from fengshen_amd.ops.flash import (
             flash_attention, flash_attn_supported, kstart_supported,

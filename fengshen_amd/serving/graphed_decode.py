@@ -6,7 +6,8 @@ a path that is otherwise weight-bandwidth-bound.  This engine captures ONE
 self-advancing decode step into a hipGraph (torch.cuda.CUDAGraph is
 hipGraph on ROCm) and replays it per token:
 
-- static KV cache [b, heads, max_len, hd] per layer, position driven by a
+- static KV cache [b, kv_heads, max_len, hd] per layer (kv_heads <
+  heads under grouped-query attention), position driven by a
   device tensor (no host sync anywhere in the loop);
 - inside the graph the hot path is hand-written HIP (kernels.hip):
   bf16_gemv (weights streamed at 5.7-6.8 TB/s vs hipBLASLt's ~2.5-3 at
@@ -76,13 +77,15 @@ class GraphedDecoder:
         L = cfg.num_hidden_layers
         nh = cfg.num_attention_heads
         hd = cfg.hidden_size // nh
-        self.nh, self.hd = nh, hd
+        # grouped-query attention: the caches hold the KV heads only
+        nkv = getattr(cfg, "num_key_value_heads", None) or nh
+        self.nh, self.nkv, self.hd = nh, nkv, hd
         self.scale = 1.0 / math.sqrt(hd)
 
         # static state
-        self.k_cache = [torch.zeros(batch, nh, max_len, hd, device=dev,
+        self.k_cache = [torch.zeros(batch, nkv, max_len, hd, device=dev,
                                     dtype=dt) for _ in range(L)]
-        self.v_cache = [torch.zeros(batch, nh, max_len, hd, device=dev,
+        self.v_cache = [torch.zeros(batch, nkv, max_len, hd, device=dev,
                                     dtype=dt) for _ in range(L)]
         self.tok = torch.zeros(batch, 1, device=dev, dtype=torch.long)
         self.pos = torch.zeros(1, device=dev, dtype=torch.long)
@@ -91,7 +94,8 @@ class GraphedDecoder:
                                       dtype=torch.long)
         self.ar = torch.arange(max_len, device=dev)
         cos, sin = F_ops.build_rope_cache(
-            max_len, hd, base=getattr(cfg, "rope_base", 10000.0))
+            max_len, hd, base=getattr(cfg, "rotary_emb_base",
+                                      getattr(cfg, "rope_base", 10000.0)))
         self.cos = cos.to(dev)
         self.sin = sin.to(dev)
         # sampling state: gumbel-max with a pre-generated noise buffer
@@ -136,7 +140,7 @@ class GraphedDecoder:
     def _step(self):
         """Graph-safe single-token decode; advances tok/pos/step_i."""
         m = self.model.model
-        b, nh, hd = self.batch, self.nh, self.hd
+        b, nh, nkv, hd = self.batch, self.nh, self.nkv, self.hd
         pos = self.pos
         h = m.embed_tokens(self.tok)  # [b, 1, H]
         if not self._fused_attn:
@@ -161,7 +165,7 @@ class GraphedDecoder:
                 if isinstance(qkv, tuple):
                     qkv = qkv[0]
                 ctx = self._ext.decode_attn(
-                    qkv.view(b, 3 * nh * hd), self.k_cache[i],
+                    qkv.view(b, (nh + 2 * nkv) * hd), self.k_cache[i],
                     self.v_cache[i], self.cos, self.sin, pos,
                     self.scale, bool(layer.attention.rotary))
                 out = layer.attention.out_proj(ctx.view(b, 1, nh * hd))
@@ -181,19 +185,23 @@ class GraphedDecoder:
             qkv = layer.attention.qkv_proj(x)
             if isinstance(qkv, tuple):
                 qkv = qkv[0]
-            q, k, v = qkv.chunk(3, dim=-1)
+            q, k, v = qkv.split([nh * hd, nkv * hd, nkv * hd], dim=-1)
             q = q.view(b, 1, nh, hd).transpose(1, 2)  # [b, nh, 1, hd]
-            k = k.view(b, 1, nh, hd).transpose(1, 2)
-            v = v.view(b, 1, nh, hd).transpose(1, 2)
+            k = k.view(b, 1, nkv, hd).transpose(1, 2)
+            v = v.view(b, 1, nkv, hd).transpose(1, 2)
             if layer.attention.rotary:
                 q = q * c + self._rot_half(q) * s
                 k = k * c + self._rot_half(k) * s
             self.k_cache[i].index_copy_(2, pos, k)
             self.v_cache[i].index_copy_(2, pos, v)
+            kfull, vfull = self.k_cache[i], self.v_cache[i]
+            if nkv != nh:  # eager fallback: expand the cache to nh heads
+                from fengshen_amd.ops.flash import expand_kv
+                kfull, vfull = expand_kv(kfull, nh), expand_kv(vfull, nh)
             scores = (q.float() @
-                      self.k_cache[i].float().transpose(-1, -2)) * self.scale
+                      kfull.float().transpose(-1, -2)) * self.scale
             probs = torch.softmax(scores + amask, dim=-1)
-            ctx = (probs.to(self.dt) @ self.v_cache[i])  # [b, nh, 1, hd]
+            ctx = (probs.to(self.dt) @ vfull)  # [b, nh, 1, hd]
             ctx = ctx.transpose(1, 2).reshape(b, 1, nh * hd)
             out = layer.attention.out_proj(ctx)
             if isinstance(out, tuple):

@@ -5,7 +5,8 @@ permute + vocab rounding :56-110, fs_to_hf.py, convert_fs_llama_tp.py) and
 utils/apply_delta.py / make_delta.py (Ziya delta-weight release flow).
 
 Our LLaMA differs from HF's in two ways: fused qkv_proj (q;k;v rows) and
-fused gate_up_proj (gate;up rows).  RoPE convention matches HF's
+fused gate_up_proj (gate;up rows).  Grouped-query checkpoints keep their
+narrower k/v rows: qkv_proj is [(h + 2*h_kv)*d, hidden].  RoPE convention matches HF's
 half-rotation layout, so no rotary permute is needed.
 """
 from __future__ import annotations
@@ -52,10 +53,13 @@ def fs_to_hf_llama(fs_sd: Dict[str, torch.Tensor],
         out[f"{p}.post_attention_layernorm.weight"] = \
             fs_sd[f"{p}.post_attention_norm.weight"]
         qkv = fs_sd[f"{p}.attention.qkv_proj.weight"]
-        h = qkv.shape[0] // 3
+        # q_proj is square, so its rows are the input width; k and v share
+        # the rest (narrower than q under grouped-query attention)
+        h = qkv.shape[1]
+        kv = (qkv.shape[0] - h) // 2
         out[f"{p}.self_attn.q_proj.weight"] = qkv[:h]
-        out[f"{p}.self_attn.k_proj.weight"] = qkv[h:2 * h]
-        out[f"{p}.self_attn.v_proj.weight"] = qkv[2 * h:]
+        out[f"{p}.self_attn.k_proj.weight"] = qkv[h:h + kv]
+        out[f"{p}.self_attn.v_proj.weight"] = qkv[h + kv:]
         out[f"{p}.self_attn.o_proj.weight"] = \
             fs_sd[f"{p}.attention.out_proj.weight"]
         gu = fs_sd[f"{p}.mlp.gate_up_proj.weight"]
