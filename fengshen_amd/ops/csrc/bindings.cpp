@@ -9,6 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "flash_blockmap.h"
+
 enum FsDtype { FS_F32 = 0, FS_BF16 = 1, FS_F16 = 2 };
 
 static int fs_dtype(const at::Tensor& t) {
@@ -707,6 +709,27 @@ static void flash_attn_bwd_v3_strided(
       causal ? 1 : 0, (float)scale, 0.f, 0ull, cur_stream());
 }
 
+// Host only: row L of the int32 [nx * ny * nz, 3] result is the logical
+// (x, y, z) that the flash v3 kernels give the block with hardware linear id
+// L, from the function the kernels call (flash_blockmap.h).
+static at::Tensor flash_v3_block_map(int64_t nx, int64_t ny, int64_t nz,
+                                     bool heavy_last) {
+  TORCH_CHECK(nx >= 1 && ny >= 1 && nz >= 1 && nx * ny * nz <= (1 << 24),
+              "flash_v3_block_map: grid (", nx, ", ", ny, ", ", nz, ")");
+  const int64_t T = nx * ny * nz;
+  auto out = at::empty({T, 3}, at::TensorOptions().dtype(at::kInt));
+  int* p = out.data_ptr<int>();
+  for (int64_t L = 0; L < T; ++L) {
+    const FlashBlock blk = flash_v3_block_of(
+        (unsigned int)L, (unsigned int)nx, (unsigned int)ny, (unsigned int)nz,
+        heavy_last);
+    p[3 * L + 0] = (int)blk.x;
+    p[3 * L + 1] = (int)blk.y;
+    p[3 * L + 2] = (int)blk.z;
+  }
+  return out;
+}
+
 // Rotates q and k ([b, np, s, hn] views sharing strides) in place;
 // bwd = transpose rotation for gradients.  cos/sin: [S, hn] fp32.
 static void rope_inplace(at::Tensor q, at::Tensor k, at::Tensor cos,
@@ -1101,6 +1124,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("dv"), py::arg("scale"), py::arg("causal"),
           py::arg("klens"), py::arg("kstart") = py::none(),
           py::arg("qend") = py::none(), py::arg("check_values") = false);
+  mod.def("flash_v3_block_map", &flash_v3_block_map, py::arg("nx"),
+          py::arg("ny"), py::arg("nz"), py::arg("heavy_last"));
   mod.def("rope_inplace", &rope_inplace);
   mod.def("rope_inplace_one", &rope_inplace_one);
   mod.def("rms_norm_fwd", &rms_norm_fwd);

@@ -29,6 +29,7 @@
 // Outputs: O [b,h,sq,D] and LSE [b,h,sq] (softmax log-sum-exp, for bwd).
 
 #include "common.h"
+#include "flash_blockmap.h"
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -1109,6 +1110,19 @@ __device__ __forceinline__ int v3_block_kstart_min(const int* ksb, int blk,
   return v3_wave_min(m);
 }
 
+// ---- which (x, head, batch) this block computes ----------------------------
+// The v3 kernels launch the grid (x, head, batch) they always had and take
+// their coordinates from the XCD-aware map of flash_blockmap.h instead of
+// blockIdx: the blocks that share an XCD run whole (batch, head) columns,
+// heaviest block first, instead of all the blocks of one x.  heavy_last:
+// fwd and dq do more work at large x, dkv at small x (causal); without a
+// mask only the L2 sharing is left.  Everything is wave-uniform.
+__device__ __forceinline__ FlashBlock v3_block(bool heavy_last) {
+  const unsigned int L =
+      blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+  return flash_v3_block_of(L, gridDim.x, gridDim.y, gridDim.z, heavy_last);
+}
+
 // ---- grouped-query attention (GQA instantiations) --------------------------
 // K/V (and dK/dV) carry h_kv = h / G heads with FaStrides of their own (kvs,
 // gkvs); query head j uses KV head j / G.  fwd and dq keep one block per
@@ -1182,20 +1196,22 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
   const int wave = threadIdx.x >> 6;
   const int hi = lane >> 5;      // lane half
   const int ln = lane & 31;
-  const long bh = (long)blockIdx.z * h + blockIdx.y;
-  const long qoff = blockIdx.z * qs.b + blockIdx.y * qs.h;
+  const FlashBlock blk = v3_block(true);
+  const unsigned int bx = blk.x, by = blk.y, bz = blk.z;
+  const long bh = (long)bz * h + by;
+  const long qoff = bz * qs.b + by * qs.h;
   const bf16_t* Qp = Q + qoff;
   // GQA: query head j reads KV head j / G through K/V's own strides
   const long kvoff =
-      GQA ? blockIdx.z * kvs.b + (blockIdx.y / G) * kvs.h : qoff;
+      GQA ? bz * kvs.b + (by / G) * kvs.h : qoff;
   const long kv_r = GQA ? kvs.r : qs.r;
   const bf16_t* Kp = K + kvoff;
   const bf16_t* Vp = V + kvoff;
-  bf16_t* Op = O + blockIdx.z * os.b + blockIdx.y * os.h;
+  bf16_t* Op = O + bz * os.b + by * os.h;
 
-  const int klen = CAUSAL ? s : min(klens ? klens[blockIdx.z] : s, s);
+  const int klen = CAUSAL ? s : min(klens ? klens[bz] : s, s);
 
-  const int q0w = blockIdx.x * V3_QBLK + wave * 32;
+  const int q0w = bx * V3_QBLK + wave * 32;
   const bool q_active = q0w < s;
   const int q0c = q_active ? q0w : s - 32;
   const int my_q = q0c + ln;      // softmax row this lane owns
@@ -1219,10 +1235,10 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
   // before it is invisible to the whole wave) and the block's first tile
   int ks_q = 0, ks_w = 0, kt0 = 0;
   if (KS) {
-    const int* ksb = kstart + (long)blockIdx.z * s;
+    const int* ksb = kstart + (long)bz * s;
     ks_q = v3_kstart_at(ksb, my_q);
     ks_w = v3_wave_min(ks_q);
-    kt0 = v3_block_kstart_min(ksb, blockIdx.x, lane, s) / V3_KVBLK;
+    kt0 = v3_block_kstart_min(ksb, bx, lane, s) / V3_KVBLK;
   }
 
   // per-lane: row my_q.  KS: a wave runs a tile as soon as one of its rows
@@ -1241,7 +1257,7 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
 
   int n_kv_tiles;
   if (CAUSAL) {
-    const int q_hi_row = min(blockIdx.x * V3_QBLK + V3_QBLK, s) - 1;
+    const int q_hi_row = min(bx * V3_QBLK + V3_QBLK, s) - 1;
     n_kv_tiles = (q_hi_row / V3_KVBLK) + 1;
   } else {
     n_kv_tiles = (klen + V3_KVBLK - 1) / V3_KVBLK;
@@ -1615,22 +1631,24 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
   const int wave = threadIdx.x >> 6;
   const int hi = lane >> 5;
   const int ln = lane & 31;
-  const long bh = (long)blockIdx.z * h + blockIdx.y;
-  const long qoff = blockIdx.z * qs.b + blockIdx.y * qs.h;
+  const FlashBlock blk = v3_block(true);
+  const unsigned int bx = blk.x, by = blk.y, bz = blk.z;
+  const long bh = (long)bz * h + by;
+  const long qoff = bz * qs.b + by * qs.h;
   const bf16_t* Qp = Q + qoff;
   // GQA: query head j reads KV head j / G through K/V's own strides
   const long kvoff =
-      GQA ? blockIdx.z * kvs.b + (blockIdx.y / G) * kvs.h : qoff;
+      GQA ? bz * kvs.b + (by / G) * kvs.h : qoff;
   const long kv_r = GQA ? kvs.r : qs.r;
   const bf16_t* Kp = K + kvoff;
   const bf16_t* Vp = V + kvoff;
-  const bf16_t* dOp = dO + blockIdx.z * dos.b + blockIdx.y * dos.h;
-  bf16_t* dQp = dQ + blockIdx.z * gs.b + blockIdx.y * gs.h;
+  const bf16_t* dOp = dO + bz * dos.b + by * dos.h;
+  bf16_t* dQp = dQ + bz * gs.b + by * gs.h;
   const float* lse = LSE + bh * s;
   const float* dlt = Delta + bh * s;
 
-  const int klen = CAUSAL ? s : min(klens ? klens[blockIdx.z] : s, s);
-  const int q0w = blockIdx.x * V3_QBLK + wave * 32;
+  const int klen = CAUSAL ? s : min(klens ? klens[bz] : s, s);
+  const int q0w = bx * V3_QBLK + wave * 32;
   const bool q_active = q0w < s;
   const int q0c = q_active ? q0w : s - 32;
   const int my_q = q0c + ln;
@@ -1656,10 +1674,10 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
   // KS: as in the forward kernel, in 32-key tiles
   int ks_q = 0, ks_w = 0, kt0 = 0;
   if (KS) {
-    const int* ksb = kstart + (long)blockIdx.z * s;
+    const int* ksb = kstart + (long)bz * s;
     ks_q = v3_kstart_at(ksb, my_q);
     ks_w = v3_wave_min(ks_q);
-    kt0 = v3_block_kstart_min(ksb, blockIdx.x, lane, s) / B3_FB;
+    kt0 = v3_block_kstart_min(ksb, bx, lane, s) / B3_FB;
   }
 
   f32x16 dq_acc[NTO];
@@ -1671,7 +1689,7 @@ void flash_attn_bwd_dq_v3_kernel(const bf16_t* __restrict__ Q,
 
   int n_kv_tiles;
   if (CAUSAL) {
-    const int q_hi_row = min(blockIdx.x * V3_QBLK + V3_QBLK, s) - 1;
+    const int q_hi_row = min(bx * V3_QBLK + V3_QBLK, s) - 1;
     n_kv_tiles = (q_hi_row / B3_FB) + 1;
   } else {
     n_kv_tiles = (klen + B3_FB - 1) / B3_FB;
@@ -1849,27 +1867,31 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
   const int wave = threadIdx.x >> 6;
   const int hi = lane >> 5;
   const int ln = lane & 31;
-  // GQA: blockIdx.y is the KV head; the block walks the G query heads
+  // the block's work falls with x: a causal kv block meets the query tiles
+  // from its own rows on
+  const FlashBlock blk = v3_block(false);
+  const unsigned int bx = blk.x, by = blk.y, bz = blk.z;
+  // GQA: by is the KV head; the block walks the G query heads
   // qh0 .. qh0 + G - 1 that share it (h stays the number of query heads)
-  const unsigned int qh0 = GQA ? blockIdx.y * G : blockIdx.y;
-  const long bh = (long)blockIdx.z * h + qh0;
-  const long qoff = blockIdx.z * qs.b + qh0 * qs.h;
+  const unsigned int qh0 = GQA ? by * G : by;
+  const long bh = (long)bz * h + qh0;
+  const long qoff = bz * qs.b + qh0 * qs.h;
   const bf16_t* Qp = Q + qoff;
-  const long kvoff = GQA ? blockIdx.z * kvs.b + blockIdx.y * kvs.h : qoff;
+  const long kvoff = GQA ? bz * kvs.b + by * kvs.h : qoff;
   const long kv_r = GQA ? kvs.r : qs.r;
   const bf16_t* Kp = K + kvoff;
   const bf16_t* Vp = V + kvoff;
-  const bf16_t* dOp = dO + blockIdx.z * dos.b + qh0 * dos.h;
-  const long goff = GQA ? blockIdx.z * gkvs.b + blockIdx.y * gkvs.h
-                        : blockIdx.z * gs.b + blockIdx.y * gs.h;
+  const bf16_t* dOp = dO + bz * dos.b + qh0 * dos.h;
+  const long goff = GQA ? bz * gkvs.b + by * gkvs.h
+                        : bz * gs.b + by * gs.h;
   const long g_r = GQA ? gkvs.r : gs.r;
   bf16_t* dKp = dK + goff;
   bf16_t* dVp = dV + goff;
   const float* lse = LSE + bh * s;
   const float* dlt = Delta + bh * s;
 
-  const int klen = CAUSAL ? s : min(klens ? klens[blockIdx.z] : s, s);
-  const int kv0_blk = blockIdx.x * V3_QBLK;
+  const int klen = CAUSAL ? s : min(klens ? klens[bz] : s, s);
+  const int kv0_blk = bx * V3_QBLK;
   const int kv0w = kv0_blk + wave * 32;
   const bool kv_active = kv0w < s;
   const int kv0c = kv_active ? kv0w : s - 32;
@@ -1890,9 +1912,9 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
   int n_q_tiles = s / B3_FB;
   const int* ksb = nullptr;
   if (KS) {
-    ksb = kstart + (long)blockIdx.z * s;
+    ksb = kstart + (long)bz * s;
     const int nt = s / V3_KVBLK;
-    const int* qe = qend + (long)blockIdx.z * nt;
+    const int* qe = qend + (long)bz * nt;
     int e = 0;
 #pragma unroll
     for (int j = 0; j < V3_QBLK / V3_KVBLK; ++j)
