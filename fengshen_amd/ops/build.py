@@ -23,7 +23,8 @@ def sources():
     srcs = [os.path.join(_CSRC, "bindings.cpp"),
             os.path.join(_CSRC, "kernels.hip"),
             os.path.join(_CSRC, "fused_norm.hip"),
-            os.path.join(_CSRC, "sparse_flash.hip")]
+            os.path.join(_CSRC, "sparse_flash.hip"),
+            os.path.join(_CSRC, "decode_attn.hip")]
     fa = os.path.join(_CSRC, "flash_attn.hip")
     if os.path.exists(fa):
         srcs.append(fa)

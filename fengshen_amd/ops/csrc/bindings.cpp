@@ -61,6 +61,9 @@ void fs_bf16_gemv(const void*, const void*, void*, int, int, int,
                   hipStream_t);
 void fs_add_rms_norm(const void*, const void*, const void*, void*, void*,
                      int, int, float, hipStream_t);
+void fs_decode_attn_split(const void*, void*, void*, const float*,
+                          const float*, const void*, int, float*, void*, int,
+                          int, int, int, int, float, int, int, hipStream_t);
 void fs_decode_attn(const void*, void*, void*, const float*, const float*,
                     const void*, void*, int, int, int, int, int, float, int,
                     hipStream_t);
@@ -838,6 +841,69 @@ static at::Tensor decode_attn(at::Tensor qkv, at::Tensor kc, at::Tensor vc,
   return ctx;
 }
 
+// Split-KV grouped decode step (decode_attn.hip).  Arguments as decode_attn,
+// except pos: int64 [b] (per sequence) or [1] (broadcast), and nsplit: the
+// number of chunks the key prefix of a row is split into (0 = automatic).
+// The automatic count depends on shapes only, so a captured graph keeps it:
+// the smallest nsplit that gives the grid two blocks per CU (256 CUs), capped
+// at ceil(L / 256) and at 64.
+static at::Tensor decode_attn_split(at::Tensor qkv, at::Tensor kc,
+                                    at::Tensor vc, at::Tensor cos_t,
+                                    at::Tensor sin_t, at::Tensor pos,
+                                    double scale, bool rope, int64_t nsplit) {
+  TORCH_CHECK(qkv.scalar_type() == at::kBFloat16 && qkv.is_contiguous(),
+              "decode_attn_split: qkv must be contiguous bf16");
+  TORCH_CHECK(kc.dim() == 4 && vc.sizes() == kc.sizes() &&
+                  kc.scalar_type() == at::kBFloat16 &&
+                  vc.scalar_type() == at::kBFloat16 && kc.is_contiguous() &&
+                  vc.is_contiguous(),
+              "decode_attn_split: caches must be contiguous bf16 "
+              "[b, nkv, L, d] of one shape");
+  const int b = kc.size(0), nkv = kc.size(1), L = kc.size(2), d = kc.size(3);
+  TORCH_CHECK(d == 64 || d == 96 || d == 128,
+              "decode_attn_split: head dim must be 64/96/128, got ", d);
+  TORCH_CHECK(b >= 1 && nkv >= 1 && L >= 1 && qkv.numel() % b == 0,
+              "decode_attn_split: empty cache or qkv not [b, ...]");
+  const int64_t w = qkv.numel() / b - 2 * (int64_t)nkv * d;  // nh * d
+  TORCH_CHECK(w > 0 && w % d == 0 && (w / d) % nkv == 0,
+              "decode_attn_split: qkv must be [b, (nh + 2*nkv)*d] with nh a "
+              "multiple of the caches' ", nkv, " KV heads");
+  const int nh = w / d;
+  TORCH_CHECK(pos.scalar_type() == at::kLong && pos.is_contiguous() &&
+                  (pos.numel() == 1 || pos.numel() == b),
+              "decode_attn_split: pos must be int64 with 1 or ", b,
+              " elements");
+  TORCH_CHECK(cos_t.scalar_type() == at::kFloat &&
+                  sin_t.scalar_type() == at::kFloat && cos_t.dim() == 2 &&
+                  sin_t.sizes() == cos_t.sizes() && cos_t.is_contiguous() &&
+                  sin_t.is_contiguous() && cos_t.size(0) >= L &&
+                  cos_t.size(1) == d,
+              "decode_attn_split: cos/sin must be contiguous fp32 [>= ", L,
+              ", ", d, "]");
+  TORCH_CHECK(nsplit >= 0 && nsplit <= 64,
+              "decode_attn_split: nsplit must be in [0, 64], got ", nsplit);
+  TORCH_CHECK(qkv.is_cuda() && kc.is_cuda() && vc.is_cuda() &&
+                  cos_t.is_cuda() && sin_t.is_cuda() && pos.is_cuda(),
+              "decode_attn_split: all tensors must be on the GPU");
+  if (nsplit == 0) {
+    const int64_t blocks = (int64_t)b * nkv * ((nh / nkv + 15) / 16);
+    nsplit = (2 * 256 + blocks - 1) / blocks;
+    nsplit = std::min<int64_t>(nsplit, (L + 255) / 256);
+    nsplit = std::max<int64_t>(std::min<int64_t>(nsplit, 64), 1);
+  }
+  auto ctx = at::empty({b, nh * d}, qkv.options());
+  at::Tensor ws;
+  if (nsplit > 1)
+    ws = at::empty({b, nh, nsplit, d + 2}, qkv.options().dtype(at::kFloat));
+  fs_decode_attn_split(qkv.data_ptr(), kc.data_ptr(), vc.data_ptr(),
+                       cos_t.data_ptr<float>(), sin_t.data_ptr<float>(),
+                       pos.data_ptr(), (int)pos.numel(),
+                       nsplit > 1 ? ws.data_ptr<float>() : nullptr,
+                       ctx.data_ptr(), b, nh, nkv, d, L, (float)scale,
+                       rope ? 1 : 0, (int)nsplit, cur_stream());
+  return ctx;
+}
+
 // a,b [rows, H] bf16 -> (sum=a+b, y=rmsnorm(sum)*w), inference-only
 static std::vector<at::Tensor> add_rms_norm(at::Tensor a, at::Tensor b,
                                             at::Tensor w, double eps) {
@@ -1001,6 +1067,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("w8_gemv", &w8_gemv);
   mod.def("bf16_gemv", &bf16_gemv);
   mod.def("decode_attn", &decode_attn);
+  mod.def("decode_attn_split", &decode_attn_split, py::arg("qkv"),
+          py::arg("kc"), py::arg("vc"), py::arg("cos"), py::arg("sin"),
+          py::arg("pos"), py::arg("scale"), py::arg("rope"),
+          py::arg("nsplit") = 0);
   mod.def("add_rms_norm", &add_rms_norm);
   mod.def("flash_attn_fwd", &flash_attn_fwd);
   mod.def("vocab_ce_fwd", [](at::Tensor logits2d, at::Tensor targets,

@@ -79,14 +79,14 @@ class Pipeline(BasePipeline):
                 and next(self.model.parameters()).dtype == torch.bfloat16)
 
     def _decoder_for(self, do_sample: bool, top_k: int, top_p: float,
-                     temperature: float):
+                     temperature: float, batch: int = 1):
         from fengshen_amd.serving.graphed_decode import GraphedDecoder
         # top_k changes the captured graph shape; temperature/top_p are
         # device scalars and can be retuned on the live decoder.
-        key = (do_sample, top_k)
+        key = (do_sample, top_k, batch)
         if self._decoder is None or self._decoder_key != key:
             self._decoder = GraphedDecoder(
-                self.model, batch=1, max_len=self.max_len,
+                self.model, batch=batch, max_len=self.max_len,
                 max_new_tokens=self.max_new_tokens, do_sample=do_sample,
                 top_k=top_k, top_p=top_p, temperature=temperature)
             self._decoder_key = key
@@ -119,7 +119,38 @@ class Pipeline(BasePipeline):
         return self.tokenizer.decode(out[0, ids.shape[1]:],
                                      skip_special_tokens=True)
 
+    @torch.no_grad()
+    def generate_batch(self, texts: List[str],
+                       max_new_tokens: Optional[int] = None,
+                       do_sample: bool = False, top_k: int = 0,
+                       top_p: float = 1.0,
+                       temperature: float = 1.0) -> List[str]:
+        """One graphed decode for up to 8 prompts.  Prompts of unequal length
+        are right-padded and their lengths passed on as prompt_lens, which
+        GraphedDecoder serves with the decode_attn_split kernel."""
+        n = min(max_new_tokens or self.max_new_tokens, self.max_new_tokens)
+        rows = [self.tokenizer(t, return_tensors="pt")["input_ids"][0]
+                for t in texts]
+        lens = torch.tensor([r.numel() for r in rows])
+        ids = torch.zeros(len(rows), int(lens.max()), dtype=torch.long)
+        for i, r in enumerate(rows):
+            ids[i, :r.numel()] = r
+        eos = getattr(self.tokenizer, "eos_token_id", None)
+        dec = self._decoder_for(do_sample, top_k, top_p, temperature,
+                                batch=len(rows))
+        ragged = bool((lens != lens[0]).any())
+        if ragged and not dec.supports_ragged:  # one prompt at a time
+            return [self.generate(t, max_new_tokens, do_sample, top_k, top_p,
+                                  temperature) for t in texts]
+        out = dec.generate(ids.to(self.device), max_new_tokens=n,
+                           eos_token_id=eos,
+                           prompt_lens=lens if ragged else None)
+        return [self.tokenizer.decode(o[int(ln):], skip_special_tokens=True)
+                for o, ln in zip(out, lens)]
+
     def __call__(self, texts: Union[str, List[str]], **kwargs):
         if isinstance(texts, str):
             return self.generate(texts, **kwargs)
+        if 1 < len(texts) <= 8 and self._graph_eligible():
+            return self.generate_batch(list(texts), **kwargs)
         return [self.generate(t, **kwargs) for t in texts]

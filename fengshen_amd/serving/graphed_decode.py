@@ -14,6 +14,12 @@ hipGraph on ROCm) and replays it per token:
   M=1), decode_attn (rope + cache write + online-softmax attention in one
   launch per layer) and add_rms_norm (residual add fused into the norm);
   eager torch fallback when the extension/dtype/head-dim doesn't fit;
+- decode_attn_split (decode_attn.hip) is the second attention kernel: the
+  key prefix is split over blocks, a block serves the query heads of one KV
+  head together, and every sequence has its own position.  It serves head
+  dim 96 and ragged prompt batches (generate(..., prompt_lens=...)), which
+  decode_attn cannot, and long windows; FENGSHEN_DECODE_SPLIT = auto | 0 | 1
+  picks between the two (see _SPLIT_MIN_LEN);
 - greedy argmax — or gumbel-max top-k/top-p sampling over a pre-generated
   seeded noise buffer indexed by the step tensor — feeds the token buffer
   consumed by the NEXT replay, so a whole max_new_tokens decode is just N
@@ -61,6 +67,14 @@ def filter_logits(logits: torch.Tensor, temperature: torch.Tensor,
     return torch.full_like(lg, float("-inf")).scatter(-1, idx, srt)
 
 
+# FENGSHEN_DECODE_SPLIT=auto: windows of at least this many positions run
+# decode_attn_split, shorter ones decode_attn.  At b1 h40 d128 the split
+# kernel wins from the smallest measured window, 512 (docs/KERNELS.md,
+# "split-KV decode"); the constant is never set below 513, so a decoder
+# with the default max_len = 512 keeps decode_attn.
+_SPLIT_MIN_LEN = 513
+
+
 class GraphedDecoder:
     def __init__(self, model, batch: int = 1, max_len: int = 512,
                  max_new_tokens: int = 256, do_sample: bool = False,
@@ -88,7 +102,9 @@ class GraphedDecoder:
         self.v_cache = [torch.zeros(batch, nkv, max_len, hd, device=dev,
                                     dtype=dt) for _ in range(L)]
         self.tok = torch.zeros(batch, 1, device=dev, dtype=torch.long)
-        self.pos = torch.zeros(1, device=dev, dtype=torch.long)
+        # one position per sequence; decode_attn and the eager step share
+        # one position and read the [1] view self.pos[:1]
+        self.pos = torch.zeros(batch, device=dev, dtype=torch.long)
         self.step_i = torch.zeros(1, device=dev, dtype=torch.long)
         self.out_tokens = torch.zeros(batch, max_new_tokens, device=dev,
                                       dtype=torch.long)
@@ -109,16 +125,31 @@ class GraphedDecoder:
             self.gumbel = torch.zeros(max_new_tokens, batch,
                                       cfg.vocab_size, device=dev)
         # fused rope+cache+attention kernel (one launch per layer instead
-        # of ~10 eager ops); requires bf16 and head dim 64/128
+        # of ~10 eager ops); requires bf16 and head dim 64/128 (decode_attn)
+        # or 64/96/128 (decode_attn_split)
         from fengshen_amd.ops import get_ext
         import os
         self._ext = get_ext() if dev.type == "cuda" else None
+        self._split_mode = os.environ.get("FENGSHEN_DECODE_SPLIT", "auto")
+        if self._split_mode not in ("auto", "0", "1"):
+            raise ValueError("FENGSHEN_DECODE_SPLIT must be auto, 0 or 1, "
+                             f"got {self._split_mode!r}")
+        self._use_split = self._split_mode == "1" or (
+            self._split_mode == "auto"
+            and (hd == 96 or max_len >= _SPLIT_MIN_LEN))
         self._fused_attn = (
-            self._ext is not None and hd in (64, 128)
+            self._ext is not None
+            and (hd in (64, 128) or (hd == 96 and self._use_split))
             and dt == torch.bfloat16
             and os.environ.get("FENGSHEN_AMD_FORCE_EAGER") != "1"
             and os.environ.get("FENGSHEN_DECODE_FUSED", "1") == "1")
         self._graph: Optional[torch.cuda.CUDAGraph] = None
+
+    @property
+    def supports_ragged(self) -> bool:
+        """Whether generate(..., prompt_lens=...) can run: it needs the
+        decode_attn_split kernel (per-sequence positions)."""
+        return self._fused_attn and self._split_mode != "0"
 
     # ------------------------------------------------------------------
     @staticmethod
@@ -141,7 +172,11 @@ class GraphedDecoder:
         """Graph-safe single-token decode; advances tok/pos/step_i."""
         m = self.model.model
         b, nh, nkv, hd = self.batch, self.nh, self.nkv, self.hd
-        pos = self.pos
+        # per-sequence positions for decode_attn_split, else the shared one
+        split = self._fused_attn and self._use_split
+        pos = self.pos if split else self.pos[:1]
+        attn = (self._ext.decode_attn_split if split
+                else self._ext.decode_attn) if self._fused_attn else None
         h = m.embed_tokens(self.tok)  # [b, 1, H]
         if not self._fused_attn:
             c = self.cos.index_select(0, pos).to(self.dt)  # [1, hd]
@@ -164,7 +199,7 @@ class GraphedDecoder:
                 qkv = layer.attention.qkv_proj(x)
                 if isinstance(qkv, tuple):
                     qkv = qkv[0]
-                ctx = self._ext.decode_attn(
+                ctx = attn(
                     qkv.view(b, (nh + 2 * nkv) * hd), self.k_cache[i],
                     self.v_cache[i], self.cos, self.sin, pos,
                     self.scale, bool(layer.attention.rotary))
@@ -242,15 +277,24 @@ class GraphedDecoder:
 
     # ------------------------------------------------------------------
     @torch.no_grad()
-    def _prefill(self, prompt_ids: torch.Tensor):
+    def _prefill(self, prompt_ids: torch.Tensor,
+                 prompt_lens: Optional[torch.Tensor] = None):
         """Eager prefill through the model's normal cache path, then copy
-        the per-layer K/V into the static buffers."""
+        the per-layer K/V into the static buffers.  With prompt_lens the
+        prompts are right-padded: under the causal mask a real token never
+        sees a pad, the cache rows at and above a row's length hold pad
+        junk, and decode_attn_split never reads rows above its position."""
         from transformers.cache_utils import DynamicCache
         assert prompt_ids.shape[0] == self.batch, (
             f"decoder captured for batch {self.batch}, "
             f"got {prompt_ids.shape[0]}")
         plen = prompt_ids.shape[1]
         assert plen + self.max_new <= self.max_len, "window too small"
+        if prompt_lens is not None:
+            prompt_lens = prompt_lens.to(self.dev, torch.long).view(-1)
+            assert prompt_lens.numel() == self.batch, "one length per prompt"
+            assert int(prompt_lens.min()) >= 1 and \
+                int(prompt_lens.max()) <= plen, "prompt_lens outside [1, plen]"
         cache = DynamicCache()
         out = self.model(input_ids=prompt_ids.to(self.dev),
                          past_key_values=cache, use_cache=True)
@@ -261,9 +305,15 @@ class GraphedDecoder:
             self.v_cache[i][:, :, :plen].copy_(v)
             self.k_cache[i][:, :, plen:].zero_()
             self.v_cache[i][:, :, plen:].zero_()
-        self.pos.fill_(plen)
         self.step_i.zero_()
-        self.tok.copy_(self._pick(out.logits[:, -1, :], self.step_i))
+        if prompt_lens is None:
+            self.pos.fill_(plen)
+            last = out.logits[:, -1, :]
+        else:
+            self.pos.copy_(prompt_lens)
+            last = out.logits[torch.arange(self.batch, device=self.dev),
+                              prompt_lens - 1]
+        self.tok.copy_(self._pick(last, self.step_i))
 
     def _capture(self):
         # warm up twice on a side stream (allocator + kernels), then capture
@@ -282,9 +332,32 @@ class GraphedDecoder:
     @torch.no_grad()
     def generate(self, prompt_ids: torch.Tensor,
                  max_new_tokens: Optional[int] = None,
-                 eos_token_id: Optional[int] = None) -> torch.Tensor:
-        """Greedy decode via graph replays.  Returns [b, plen + n]."""
+                 eos_token_id: Optional[int] = None,
+                 prompt_lens: Optional[torch.Tensor] = None):
+        """Greedy (or sampled) decode via graph replays.
+
+        Without prompt_lens all prompts have the length of prompt_ids and
+        the result is a tensor [b, plen + n]: prompt, then n new tokens.
+
+        With prompt_lens (int [b]) the prompts are right-padded to plen and
+        row i holds prompt_lens[i] real tokens.  The result is then a list
+        of b 1-D tensors, row i being its prompt_lens[i] prompt tokens
+        followed by its n new tokens, with no padding in between.  This
+        needs the decode_attn_split kernel (per-sequence positions)."""
         n = min(max_new_tokens or self.max_new, self.max_new)
+        if prompt_lens is not None:
+            prompt_lens = torch.as_tensor(prompt_lens)
+        if prompt_lens is not None and not (self._fused_attn
+                                            and self._use_split):
+            if not self.supports_ragged:
+                raise RuntimeError(
+                    "prompt_lens (prompts of unequal length) needs the fused "
+                    "decode_attn_split kernel: bf16 weights, head dim "
+                    "64/96/128, the HIP extension and FENGSHEN_DECODE_SPLIT "
+                    "not 0")
+            # auto mode on a short window: switch kernels, capture again
+            self._use_split = True
+            self._graph = None
         if self.do_sample:
             # fresh Gumbel(0,1) noise per call: -log(Exp(1)); seeded via
             # torch.manual_seed for reproducible sampling.
@@ -296,7 +369,7 @@ class GraphedDecoder:
             # static window even for tiny max_new_tokens.
             self.pos.fill_(min(prompt_ids.shape[1], self.max_len - 3))
             self._capture()
-        self._prefill(prompt_ids)
+        self._prefill(prompt_ids, prompt_lens)
         # first generated token came from prefill logits
         self.out_tokens.index_copy_(
             1, self.step_i, self.tok)
@@ -308,4 +381,8 @@ class GraphedDecoder:
             # trim after the first EOS per row (host-side, post hoc)
             done = (toks == eos_token_id).cumsum(dim=1) > 0
             toks = toks.masked_fill(done, eos_token_id)
-        return torch.cat([prompt_ids.to(self.dev), toks], dim=1)
+        prompt_ids = prompt_ids.to(self.dev)
+        if prompt_lens is None:
+            return torch.cat([prompt_ids, toks], dim=1)
+        return [torch.cat([prompt_ids[i, :int(ln)], toks[i]])
+                for i, ln in enumerate(prompt_lens.tolist())]

@@ -1,0 +1,157 @@
+"""decode_attn (one block per head, serial over the prefix) against
+decode_attn_split (split-KV, grouped heads) on the same tensors, and the
+end-to-end ms/token of GraphedDecoder with either kernel.
+
+    python scripts/decode_attn_bench.py            # every step
+    python scripts/decode_attn_bench.py --step 1   # one step, in-process
+
+Every step runs in a child process of its own under a time limit; the first
+step that fails ends the script.  Times are device events around ITERS
+back-to-back calls; the two kernels alternate inside each of 5 repeats after a
+warm-up, and the table gives median [min, max] per call.  K/V GB/s counts
+2 * (pos + 1) * h_kv * d * 2 * b bytes; the floor is those bytes at 6.3 TB/s.
+"""
+import argparse
+import math
+import os
+import statistics
+import subprocess
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                                ".."))
+
+SHAPES = [(40, 40, 128), (32, 8, 128), (32, 1, 128), (36, 36, 96)]
+BATCHES = [1, 8]
+POSITIONS = [511, 2047, 8191, 32767]
+REPEATS, ITERS = 5, 20
+HBM_BPS = 6.3e12
+STEP_TIMEOUT = 240  # seconds per child
+
+
+def _time(fn):
+    import torch
+    beg = torch.cuda.Event(enable_timing=True)
+    end = torch.cuda.Event(enable_timing=True)
+    beg.record()
+    for _ in range(ITERS):
+        fn()
+    end.record()
+    end.synchronize()
+    return beg.elapsed_time(end) * 1e3 / ITERS  # us per call
+
+
+def _fmt(ts):
+    return f"{statistics.median(ts):8.1f} [{min(ts):7.1f}, {max(ts):7.1f}]"
+
+
+def kernel_step(idx):
+    import torch
+    from fengshen_amd.ops import functional as F_ops
+    from fengshen_amd.ops import get_ext
+    ext = get_ext()
+    h, h_kv, d = SHAPES[idx]
+    scale = 1 / math.sqrt(d)
+    print(f"## h={h} h_kv={h_kv} d={d}   (us per call: median [min, max])")
+    print("| b | pos | floor us | decode_attn | GB/s | decode_attn_split "
+          "| GB/s | max abs diff |")
+    print("|---|---|---|---|---|---|---|---|")
+    for b in BATCHES:
+        for p in POSITIONS:
+            L = p + 1
+            torch.manual_seed(p + b)
+            qkv = (torch.randn(b, (h + 2 * h_kv) * d, device="cuda")
+                   * 0.5).bfloat16()
+            kc = (torch.randn(b, h_kv, L, d, device="cuda") * 0.5).bfloat16()
+            vc = (torch.randn(b, h_kv, L, d, device="cuda") * 0.5).bfloat16()
+            cos, sin = F_ops.build_rope_cache(L, d)
+            cos, sin = cos.cuda(), sin.cuda()
+            pos1 = torch.tensor([p], device="cuda")
+            posb = torch.full((b,), p, device="cuda")
+            nbytes = 2 * (p + 1) * h_kv * d * 2 * b
+
+            def new():
+                return ext.decode_attn_split(qkv, kc, vc, cos, sin, posb,
+                                             scale, True)
+
+            def old():
+                return ext.decode_attn(qkv, kc, vc, cos, sin, pos1, scale,
+                                       True)
+            has_old = d in (64, 128)
+            diff = float("nan")
+            if has_old:
+                diff = float((old().float() - new().float()).abs().max())
+                _time(old)
+            _time(new)
+            t_old, t_new = [], []
+            for _ in range(REPEATS):
+                if has_old:
+                    t_old.append(_time(old))
+                t_new.append(_time(new))
+            o = (f"{_fmt(t_old)} | "
+                 f"{nbytes / statistics.median(t_old) / 1e3:6.0f}"
+                 if has_old else "- | -")
+            print(f"| {b} | {p} | {nbytes / HBM_BPS * 1e6:6.1f} | {o} | "
+                  f"{_fmt(t_new)} | "
+                  f"{nbytes / statistics.median(t_new) / 1e3:6.0f} | "
+                  f"{diff:.4f} |", flush=True)
+            del qkv, kc, vc
+
+
+def e2e_step():
+    """4 layers of the Ziya-13B layer shape, max_len 8192, 4096-token prompt:
+    ms/token of the captured step with FENGSHEN_DECODE_SPLIT=0 and =1."""
+    import torch
+    from fengshen_amd.models.llama.configuration_llama import LlamaConfig
+    from fengshen_amd.models.llama.modeling_llama import LlamaForCausalLM
+    from fengshen_amd.serving.graphed_decode import GraphedDecoder
+    torch.manual_seed(0)
+    cfg = LlamaConfig(vocab_size=39424, hidden_size=5120,
+                      num_hidden_layers=4, num_attention_heads=40,
+                      intermediate_size=13824, max_position_embeddings=8192)
+    model = LlamaForCausalLM(cfg).to(torch.bfloat16).cuda().eval()
+    ids = torch.randint(3, 39424, (1, 4096), device="cuda")
+    decs = {}
+    for mode in ("0", "1"):
+        os.environ["FENGSHEN_DECODE_SPLIT"] = mode
+        decs[mode] = GraphedDecoder(model, batch=1, max_len=8192,
+                                    max_new_tokens=64)
+        decs[mode].generate(ids, max_new_tokens=8)  # capture + warm-up
+    times = {"0": [], "1": []}
+    for _ in range(REPEATS):
+        for mode, dec in decs.items():
+            dec._prefill(ids)
+            beg = torch.cuda.Event(enable_timing=True)
+            end = torch.cuda.Event(enable_timing=True)
+            beg.record()
+            for _ in range(48):
+                dec._graph.replay()
+            end.record()
+            end.synchronize()
+            times[mode].append(beg.elapsed_time(end) / 48)
+    for mode, ts in times.items():
+        print(f"GraphedDecoder 4 layers, pos 4096.., FENGSHEN_DECODE_SPLIT="
+              f"{mode}: {statistics.median(ts):.3f} ms/token "
+              f"[{min(ts):.3f}, {max(ts):.3f}]", flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--step", type=int, default=None,
+                    help="0..3: kernel table of SHAPES[step]; 4: end to end")
+    args = ap.parse_args()
+    if args.step is not None:
+        e2e_step() if args.step == len(SHAPES) else kernel_step(args.step)
+        return 0
+    for step in range(len(SHAPES) + 1):
+        rc = subprocess.run([sys.executable, os.path.abspath(__file__),
+                             "--step", str(step)],
+                            timeout=STEP_TIMEOUT).returncode
+        if rc != 0:
+            print(f"step {step} failed with exit status {rc}; stopping")
+            return rc
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
