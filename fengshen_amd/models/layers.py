@@ -420,7 +420,17 @@ class LLaMAParallelMLP(nn.Module):
             init_method=output_init_method or init_method, dtype=dtype,
             reduce_output=reduce_output)
 
-    def forward(self, x):
+    def forward(self, x, residual=None, output_unused: bool = False):
+        """With ``residual`` (tensor-parallel size 1 only): residual + mlp(x)
+        as one autograd node, F_ops.swiglu_mlp_residual; ``output_unused``
+        is that op's promise that nobody reads the result."""
+        if residual is not None:
+            if groups.get_tensor_model_parallel_world_size() != 1:
+                raise ValueError("the one-node MLP tail has no tensor-"
+                                 "parallel reduce: call without residual")
+            return F_ops.swiglu_mlp_residual(
+                x, residual, self.gate_up_proj.weight, self.down_proj.weight,
+                output_unused)
         packed = self.gate_up_proj(x)
         h = F_ops.swiglu(packed)
         return self.down_proj(h)  # (partial, bias) when reduce_output=False
@@ -476,7 +486,12 @@ class ParallelTransformerLayer(nn.Module):
             return out[0], out[1]
         return out, None
 
-    def forward(self, x, attention_mask=None, cache=None, kstart=None):
+    def forward(self, x, attention_mask=None, cache=None, kstart=None,
+                output_unused: bool = False):
+        """output_unused=True: the caller discards the layer's output (an
+        activation-checkpoint recompute of exactly this layer), so the
+        fused MLP tail may skip computing it; paths that do not fuse the
+        tail ignore the flag and compute everything."""
         if self.parallel_residual:
             from fengshen_amd.parallel.mappings import (
                 reduce_from_tensor_model_parallel_region)
@@ -515,6 +530,14 @@ class ParallelTransformerLayer(nn.Module):
                                        self.hidden_dropout, self.training)
             h = self.post_attention_norm(x)
         residual = x
+        # training-only: eval and decode keep the GEMV fast path of the
+        # separate linears
+        if (self.training and isinstance(self.mlp, LLaMAParallelMLP)
+                and groups.get_tensor_model_parallel_world_size() == 1
+                and self.hidden_dropout == 0.0
+                and F_ops.fused_mlp_enabled()):
+            return self.mlp(h, residual=residual,
+                            output_unused=output_unused)
         mlp_out = self.mlp(h)
         x = F_ops.bias_dropout_add(mlp_out, None, residual,
                                    self.hidden_dropout, self.training)

@@ -37,6 +37,7 @@ from fengshen_amd.parallel.cross_entropy import vocab_parallel_cross_entropy
 from fengshen_amd.parallel.layers import ColumnParallelLinear, VocabParallelEmbedding
 from fengshen_amd.parallel.mappings import gather_from_tensor_model_parallel_region
 from fengshen_amd.parallel.random import checkpoint as activation_checkpoint
+from fengshen_amd.parallel.random import in_recompute
 
 
 class LlamaPreTrainedModel(PreTrainedModel):
@@ -127,9 +128,12 @@ class LlamaModel(LlamaPreTrainedModel):
             if ckpt and skip and (i % skip == skip - 1):
                 ckpt = False  # selective: keep this layer's activations
             if ckpt:
+                # the layer's output is the checkpointed function's output,
+                # which a recompute throws away
                 h = activation_checkpoint(
-                    lambda x, m, ks, lyr=layer: lyr(x, attention_mask=m,
-                                                    kstart=ks),
+                    lambda x, m, ks, lyr=layer: lyr(
+                        x, attention_mask=m, kstart=ks,
+                        output_unused=in_recompute()),
                     h, mask, kstart)
             else:
                 h = layer(h, attention_mask=mask, cache=cache, kstart=kstart)

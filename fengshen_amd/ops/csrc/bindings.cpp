@@ -46,6 +46,8 @@ void fs_rope(const void*, void*, const float*, const float*, long, int, int,
 void fs_swiglu_fwd(const void*, void*, long, int, int, hipStream_t);
 void fs_swiglu_bwd(const void*, const void*, void*, long, int, int,
                    hipStream_t);
+void fs_swiglu_bwd_act(const void*, const void*, void*, void*, long, int, int,
+                       hipStream_t);
 void fs_bias_gelu(const void*, const void*, const void*, void*, long, int, int,
                   int, hipStream_t);
 void fs_fused_adamw(float*, const void*, float*, float*, void*, long, float,
@@ -371,6 +373,48 @@ static at::Tensor swiglu_bwd(at::Tensor gy, at::Tensor packed) {
   fs_swiglu_bwd(gy.contiguous().data_ptr(), packed.data_ptr(),
                 gpacked.data_ptr(), rows, h, fs_dtype(packed), cur_stream());
   return gpacked;
+}
+
+// swiglu_bwd that also returns act = silu(gate) * up, bit for bit what
+// swiglu_fwd(packed) returns.  gy: [..., h], packed: [..., 2h] -> (gpacked,
+// act).  act_out may be omitted (allocated here) or given; it may be gy
+// itself, in which case act overwrites gy in place: aliasing is allowed.
+static std::vector<at::Tensor> swiglu_bwd_act(
+    at::Tensor gy, at::Tensor packed, c10::optional<at::Tensor> act_out) {
+  TORCH_CHECK(packed.is_cuda(), "packed must be a GPU tensor");
+  TORCH_CHECK(packed.is_contiguous(), "packed must be contiguous");
+  TORCH_CHECK(gy.is_contiguous(), "gy must be contiguous");
+  TORCH_CHECK(gy.scalar_type() == packed.scalar_type(),
+              "gy and packed must have the same dtype");
+  TORCH_CHECK(packed.dim() >= 1 && packed.size(-1) % 16 == 0,
+              "packed dim must be divisible by 16");
+  const int h2 = packed.size(-1);
+  const int h = h2 / 2;
+  const long rows = packed.numel() / h2;
+  auto sizes = packed.sizes().vec();
+  sizes.back() = h;
+  TORCH_CHECK(gy.sizes() == at::IntArrayRef(sizes),
+              "gy must have packed's shape with half the last dim");
+  at::Tensor act;
+  if (act_out.has_value()) {
+    act = *act_out;
+    TORCH_CHECK(act.is_contiguous(), "act must be contiguous");
+    TORCH_CHECK(act.scalar_type() == packed.scalar_type(),
+                "act and packed must have the same dtype");
+    TORCH_CHECK(act.device() == packed.device(),
+                "act and packed must be on the same device");
+    TORCH_CHECK(act.sizes() == at::IntArrayRef(sizes),
+                "act must have packed's shape with half the last dim");
+  } else {
+    act = at::empty(sizes, packed.options());
+  }
+  TORCH_CHECK(gy.device() == packed.device(),
+              "gy and packed must be on the same device");
+  auto gpacked = at::empty_like(packed);
+  if (rows > 0)
+    fs_swiglu_bwd_act(gy.data_ptr(), packed.data_ptr(), gpacked.data_ptr(),
+                      act.data_ptr(), rows, h, fs_dtype(packed), cur_stream());
+  return {gpacked, act};
 }
 
 static at::Tensor bias_gelu_fwd(at::Tensor x, at::Tensor bias) {
@@ -1212,6 +1256,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("rope_bwd", &rope_bwd);
   mod.def("swiglu_fwd", &swiglu_fwd);
   mod.def("swiglu_bwd", &swiglu_bwd);
+  mod.def("swiglu_bwd_act", &swiglu_bwd_act, py::arg("gy"),
+          py::arg("packed"), py::arg("act_out") = py::none());
   mod.def("bias_gelu_fwd", &bias_gelu_fwd);
   mod.def("bias_gelu_bwd", &bias_gelu_bwd);
   mod.def("fused_adamw", &fused_adamw);

@@ -437,6 +437,22 @@ __global__ void rope_inplace_kernel(T* __restrict__ xq, T* __restrict__ xk,
 // ===========================================================================
 // SwiGLU: packed [rows, 2h] -> out [rows, h]
 // ===========================================================================
+// The one definition of act = silu(gate) * up: the forward kernel and
+// swiglu_bwd_act_kernel both call it, so the two produce the same bits.
+// The order is pinned to (gate * up) * sig, which is how the -ffast-math
+// build has always evaluated the forward kernel's `gv * sig * uv`; left to
+// the compiler, each kernel could pick an association of its own.
+__device__ __forceinline__ float swiglu_sigmoid(float gv) {
+  return 1.f / (1.f + __expf(-gv));
+}
+__device__ __forceinline__ float swiglu_act(float gv, float sig, float uv) {
+#pragma clang fp reassociate(off)
+  return (gv * uv) * sig;
+}
+
+// Packed fp32 VALU forms are kept out of the forward kernel.
+#pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), \
+                             apply_to = function)
 template <typename T>
 __global__ void swiglu_fwd_kernel(const T* __restrict__ packed,
                                   T* __restrict__ out, long rows, int h) {
@@ -452,13 +468,12 @@ __global__ void swiglu_fwd_kernel(const T* __restrict__ packed,
     load8<T>(g, gv);
     load8<T>(u, uv);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float sig = 1.f / (1.f + __expf(-gv[j]));
-      o[j] = gv[j] * sig * uv[j];
-    }
+    for (int j = 0; j < 8; ++j)
+      o[j] = swiglu_act(gv[j], swiglu_sigmoid(gv[j]), uv[j]);
     store8<T>(out + i, o);
   }
 }
+#pragma clang attribute pop
 
 template <typename T>
 __global__ void swiglu_bwd_kernel(const T* __restrict__ gy,
@@ -485,6 +500,45 @@ __global__ void swiglu_bwd_kernel(const T* __restrict__ gy,
     }
     store8<T>(gpacked + row * 2 * h + col, dg);
     store8<T>(gpacked + row * 2 * h + col + h, du);
+  }
+}
+
+// swiglu_bwd_kernel that also writes act = silu(gate) * up, the forward
+// kernel's output, for the down-projection weight gradient.  act may alias
+// gy: each thread loads its 8 gy values before it stores the same 8 act
+// values and no other thread touches them, hence no __restrict__ on the two.
+// The dg/du statements are swiglu_bwd_kernel's, compiled with the same target
+// features, so that gpacked keeps its bits: without packed fp32 forms the
+// compiler stops folding the first and last du of a vector into
+// v_fma_mix(.., +0), which stores a product of -0 as +0 in fp16.
+template <typename T>
+__global__ void swiglu_bwd_act_kernel(const T* gy,
+                                      const T* __restrict__ packed,
+                                      T* __restrict__ gpacked, T* act,
+                                      long rows, int h) {
+  const long total = rows * (long)h;
+  const long stride = (long)gridDim.x * blockDim.x * 8;
+  for (long i = (long)(blockIdx.x * blockDim.x + threadIdx.x) * 8; i < total;
+       i += stride) {
+    const long row = i / h;
+    const long col = i % h;
+    const T* g = packed + row * 2 * h + col;
+    const T* u = g + h;
+    float gv[8], uv[8], go[8], dg[8], du[8], a[8];
+    load8<T>(g, gv);
+    load8<T>(u, uv);
+    load8<T>(gy + i, go);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float sig = swiglu_sigmoid(gv[j]);
+      const float silu = gv[j] * sig;
+      dg[j] = go[j] * uv[j] * sig * (1.f + gv[j] * (1.f - sig));
+      du[j] = go[j] * silu;
+      a[j] = swiglu_act(gv[j], sig, uv[j]);
+    }
+    store8<T>(gpacked + row * 2 * h + col, dg);
+    store8<T>(gpacked + row * 2 * h + col + h, du);
+    store8<T>(act + i, a);
   }
 }
 
@@ -882,6 +936,15 @@ void fs_swiglu_bwd(const void* gy, const void* packed, void* gpacked, long rows,
   DISPATCH_DTYPE(dtype, T,
     hipLaunchKernelGGL((swiglu_bwd_kernel<T>), dim3(grid), dim3(256), 0, s,
                        (const T*)gy, (const T*)packed, (T*)gpacked, rows, h));
+}
+
+void fs_swiglu_bwd_act(const void* gy, const void* packed, void* gpacked,
+                       void* act, long rows, int h, int dtype, hipStream_t s) {
+  int grid = grid_for(rows * (long)h / 8);
+  DISPATCH_DTYPE(dtype, T,
+    hipLaunchKernelGGL((swiglu_bwd_act_kernel<T>), dim3(grid), dim3(256), 0, s,
+                       (const T*)gy, (const T*)packed, (T*)gpacked, (T*)act,
+                       rows, h));
 }
 
 void fs_bias_gelu(const void* x, const void* bias, const void* gy, void* out,

@@ -9,6 +9,7 @@ Each op mirrors a hot-path op the reference fuses (or left unfused):
   bias_dropout_add        — ref layers/fused_bias_dropout.py:44-55
   rotary (apply_rotary)   — ref layers/positional_embeddings.py:54-87
   swiglu                  — ref LLaMAParallelMLP silu(w1)*w3 (transformer.py:571-623)
+  swiglu_mlp_residual     — the same MLP with its residual add as one node
   fused attention         — ref flash_attention.py (flash_attn v1 import)
 
 The eager implementations double as numerics oracles in tests
@@ -382,6 +383,86 @@ class _BiasDropoutAdd(torch.autograd.Function):
 
 def bias_dropout_add(x, bias, residual, p: float, training: bool):
     return _BiasDropoutAdd.apply(x, bias, residual, p, training)
+
+
+def fused_mlp_enabled() -> bool:
+    """FENGSHEN_FUSED_MLP=0 keeps the SwiGLU MLP and its residual add as
+    separate autograd nodes (linear, swiglu, linear, bias_dropout_add)."""
+    return os.environ.get("FENGSHEN_FUSED_MLP", "1") != "0"
+
+
+def _unused_output_like(t: torch.Tensor) -> torch.Tensor:
+    """What swiglu_mlp_residual returns under output_unused=True: the right
+    shape and dtype, contents unspecified.  Nothing may read it."""
+    return torch.empty_like(t)
+
+
+def _swiglu_bwd_act_eager(d_act, packed):
+    """-> (d_packed, act) with the formulas of _SwiGLU's eager path."""
+    gate, up = packed.chunk(2, dim=-1)
+    g32, u32, go = gate.float(), up.float(), d_act.float()
+    sig = torch.sigmoid(g32)
+    dgate = go * u32 * sig * (1 + g32 * (1 - sig))
+    dup = go * (g32 * sig)
+    return (torch.cat([dgate, dup], dim=-1).to(packed.dtype),
+            eager_swiglu(gate, up))
+
+
+class _SwiGLUMLPResidual(torch.autograd.Function):
+    """residual + down(swiglu(gate_up(h2))) as one node.
+
+    Saves h2, packed = h2 @ w_gate_up^T and the two weights; act =
+    silu(gate) * up is rebuilt in the backward by the kernel that already
+    reads packed.  The backward needs none of the forward's outputs, so with
+    output_unused=True the forward stops after packed."""
+
+    @staticmethod
+    def forward(ctx, h2, residual, w_gate_up, w_down, output_unused):
+        packed = torch.nn.functional.linear(h2, w_gate_up)
+        ctx.save_for_backward(h2, packed, w_gate_up, w_down)
+        if output_unused:
+            return _unused_output_like(residual)
+        if use_hip(packed):
+            act = get_ext().swiglu_fwd(packed)
+        else:
+            act = eager_swiglu(*packed.chunk(2, dim=-1))
+        return torch.nn.functional.linear(act, w_down) + residual
+
+    @staticmethod
+    def backward(ctx, g):
+        h2, packed, w_gate_up, w_down = ctx.saved_tensors
+        g2d = g.reshape(-1, g.shape[-1])
+        packed2d = packed.view(-1, packed.shape[-1])
+        h2_2d = h2.reshape(-1, h2.shape[-1])
+        # the GEMMs F.linear's autograd issues, on the same operands
+        d_act = g2d.mm(w_down)
+        if use_hip(packed):
+            # act overwrites d_act in place
+            d_packed, act = get_ext().swiglu_bwd_act(d_act, packed2d, d_act)
+        else:
+            d_packed, act = _swiglu_bwd_act_eager(d_act, packed2d)
+        del d_act
+        d_w_down = g2d.t().mm(act) if ctx.needs_input_grad[3] else None
+        del act
+        d_w_gate_up = d_packed.t().mm(h2_2d) if ctx.needs_input_grad[2] \
+            else None
+        d_h2 = d_packed.mm(w_gate_up).view(h2.shape) \
+            if ctx.needs_input_grad[0] else None
+        return d_h2, g, d_w_gate_up, d_w_down, None
+
+
+def swiglu_mlp_residual(h2, residual, w_gate_up, w_down,
+                        output_unused: bool = False):
+    """residual + linear(swiglu(linear(h2, w_gate_up)), w_down): the bias-free
+    SwiGLU MLP with its residual add (hidden dropout inactive).
+
+    output_unused=True is the caller's promise that nobody reads the result,
+    as when an activation-checkpoint recompute re-runs a layer only to
+    rebuild what the backward saved.  The down projection and the add are
+    then skipped and the returned tensor has residual's shape and dtype but
+    unspecified contents; gradients are the same either way."""
+    return _SwiGLUMLPResidual.apply(h2, residual, w_gate_up, w_down,
+                                    output_unused)
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor,

@@ -8,6 +8,7 @@ self-contained torch.autograd.Function with CPU+HIP RNG state capture.
 from __future__ import annotations
 
 import contextlib
+import threading
 from typing import Dict
 
 import torch
@@ -97,6 +98,27 @@ def model_parallel_manual_seed(seed: int) -> None:
     _RNG_TRACKER.add(_MODEL_PARALLEL_RNG_TRACKER_NAME, model_parallel_seed)
 
 
+_RECOMPUTE = threading.local()
+
+
+def in_recompute() -> bool:
+    """True while CheckpointFunction.backward re-runs its function on this
+    thread.  The outputs of that run are discarded (only the graph behind
+    them is used), which a function that knows its own result IS the
+    checkpointed output may exploit; nothing else should read this."""
+    return getattr(_RECOMPUTE, "active", False)
+
+
+@contextlib.contextmanager
+def _recompute_scope(active: bool):
+    prev = in_recompute()
+    _RECOMPUTE.active = active
+    try:
+        yield
+    finally:
+        _RECOMPUTE.active = prev
+
+
 class CheckpointFunction(torch.autograd.Function):
     """Activation checkpointing with full RNG restoration (CPU + device +
     model-parallel tracker)."""
@@ -107,7 +129,8 @@ class CheckpointFunction(torch.autograd.Function):
         ctx.fwd_cpu_rng = torch.get_rng_state()
         ctx.fwd_dev_rng = _get_device_rng_state()
         ctx.fwd_tracker_states = _RNG_TRACKER.get_states()
-        with torch.no_grad():
+        # a checkpoint nested in another one's recompute: its output is used
+        with torch.no_grad(), _recompute_scope(False):
             outputs = run_function(*args)
         ctx.save_for_backward(*[a for a in args if torch.is_tensor(a)])
         ctx.input_is_tensor = [torch.is_tensor(a) for a in args]
@@ -131,7 +154,7 @@ class CheckpointFunction(torch.autograd.Function):
         torch.set_rng_state(ctx.fwd_cpu_rng)
         _set_device_rng_state(ctx.fwd_dev_rng)
         _RNG_TRACKER.set_states(ctx.fwd_tracker_states)
-        with torch.enable_grad():
+        with torch.enable_grad(), _recompute_scope(True):
             outputs = ctx.run_function(*detached)
         torch.set_rng_state(cur_cpu)
         _set_device_rng_state(cur_dev)
