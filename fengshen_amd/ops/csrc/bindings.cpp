@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "flash_blockmap.h"
+#include "flash_v3.h"
 
 enum FsDtype { FS_F32 = 0, FS_BF16 = 1, FS_F16 = 2 };
 
@@ -75,42 +76,6 @@ void fs_vocab_ce_fwd(const void*, const long*, float*, float*, float*,
                      long, int, int, int, hipStream_t);
 void fs_vocab_ce_bwd(const void*, const long*, const float*, const float*,
                      const float*, void*, long, int, int, int, hipStream_t);
-void fs_flash_attn_fwd_v3(const void*, const void*, const void*, void*,
-                          float*, const int*, int, int, int, int, int, float,
-                          float, unsigned long long, hipStream_t);
-void fs_flash_attn_bwd_v3(const void*, const void*, const void*, const void*,
-                          const void*, const float*, void*, void*, void*,
-                          float*, const int*, int, int, int, int, int, float,
-                          float, unsigned long long, hipStream_t);
-void fs_flash_attn_fwd_v3_strided(const void*, const void*, const void*,
-                                  void*, float*, const int*, const long*,
-                                  const long*, int, int, int, int, int, float,
-                                  float, unsigned long long, hipStream_t);
-void fs_flash_attn_bwd_v3_strided(const void*, const void*, const void*,
-                                  const void*, const void*, const float*,
-                                  void*, void*, void*, float*, const int*,
-                                  const long*, const long*, const long*,
-                                  const long*, int, int, int, int, int, float,
-                                  float, unsigned long long, hipStream_t);
-void fs_flash_attn_fwd_v3_kstart(const void*, const void*, const void*, void*,
-                                 float*, const int*, const long*, const long*,
-                                 int, int, int, int, float, hipStream_t);
-void fs_flash_attn_bwd_v3_kstart(const void*, const void*, const void*,
-                                 const void*, const void*, const float*,
-                                 void*, void*, void*, float*, const int*,
-                                 const int*, const long*, const long*,
-                                 const long*, const long*, int, int, int, int,
-                                 float, hipStream_t);
-void fs_flash_attn_fwd_v3_gqa(const void*, const void*, const void*, void*,
-                              float*, const int*, const long*, const long*,
-                              const long*, int, int, int, int, int, float,
-                              hipStream_t);
-void fs_flash_attn_bwd_v3_gqa(const void*, const void*, const void*,
-                              const void*, const void*, const float*, void*,
-                              void*, void*, float*, const int*, const int*,
-                              const long*, const long*, const long*,
-                              const long*, const long*, const long*, int, int,
-                              int, int, int, float, hipStream_t);
 void fs_rope_inplace(void*, void*, const float*, const float*, int, int, int,
                      int, long, long, long, int, int, int, hipStream_t);
 int fs_fused_norm_vectors(int);
@@ -522,13 +487,18 @@ static std::vector<at::Tensor> flash_attn_bwd(
 // The kernels use 16-byte vector accesses, so the last dim must be
 // unit-stride and every other stride and the base address 16-byte aligned.
 // All of this is checked here, on the host, before anything is launched.
-static void check_strided_view(const at::Tensor& t, const char* name, int b,
-                               int h, int s, int d) {
+static void check_bf16_bhsd(const at::Tensor& t, const char* name, int b,
+                            int h, int s, int d) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16, name,
               ": must be a bf16 GPU tensor");
   TORCH_CHECK(t.dim() == 4 && t.size(0) == b && t.size(1) == h &&
                   t.size(2) == s && t.size(3) == d,
               name, ": expected shape [", b, ", ", h, ", ", s, ", ", d, "]");
+}
+
+static void check_strided_view(const at::Tensor& t, const char* name, int b,
+                               int h, int s, int d) {
+  check_bf16_bhsd(t, name, b, h, s, d);
   TORCH_CHECK(t.stride(3) == 1, name, ": last dim must be unit-stride");
   for (int i = 0; i < 3; ++i)
     TORCH_CHECK(t.stride(i) > 0 && t.stride(i) % 8 == 0, name, ": stride ", i,
@@ -575,7 +545,8 @@ static const int* checked_klens(const c10::optional<at::Tensor>& klens,
   if (!klens.has_value()) return nullptr;
   TORCH_CHECK(!causal, "flash v3: klens only with causal=False");
   TORCH_CHECK(klens->is_cuda() && klens->scalar_type() == at::kInt &&
-              klens->numel() == b && klens->is_contiguous());
+                  klens->numel() == b && klens->is_contiguous(),
+              "flash v3: klens must be contiguous int32 [", b, "] on the GPU");
   return klens->data_ptr<int>();
 }
 
@@ -637,51 +608,139 @@ static void check_kstart(const at::Tensor& kstart,
   }
 }
 
-// Writes o in place; returns lse [b, h, s] fp32.
-static at::Tensor flash_attn_fwd_v3_strided(
-    at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, double scale,
-    bool causal, c10::optional<at::Tensor> klens,
-    c10::optional<at::Tensor> kstart, bool check_values) {
+// Backward-only operands of a flash v3 call.
+struct FlashV3Grads {
+  const at::Tensor &dout, &lse, &dq, &dk, &dv;
+};
+
+// The one gate in front of the flash v3 launchers: checks every operand and
+// option of a forward (g == nullptr) or backward call on the host, before
+// anything is launched, and describes the call for fs_flash_v3_{fwd,bwd}
+// (the caller adds the tensor it allocates: lse or delta_ws).  Strided
+// entries take any view check_strided_view accepts.  Contiguous entries
+// require is_contiguous() and derive the strides from the sizes, since a
+// contiguous tensor may carry any stride on a size-1 dim.
+static FlashV3Args checked_flash_v3(
+    const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+    const at::Tensor& o, const FlashV3Grads* g, bool contiguous, double scale,
+    bool causal, const c10::optional<at::Tensor>& klens, double drop_p,
+    int64_t seed, const c10::optional<at::Tensor>& kstart,
+    const c10::optional<at::Tensor>& qend, bool check_values) {
   TORCH_CHECK(q.dim() == 4, "q must be [b, h, s, d]");
   const int b = q.size(0), h = q.size(1), s = q.size(2), d = q.size(3);
   TORCH_CHECK((d == 128 || d == 96 || d == 64) && s % 64 == 0 && s >= 64,
               "flash v3: d in {64, 96, 128}, s a multiple of 64");
-  const int h_kv = checked_kv_heads(k, h, causal, 0.0, klens.has_value());
-  check_strided_view(q, "q", b, h, s, d);
-  check_strided_view(k, "k", b, h_kv, s, d);
-  check_strided_view(v, "v", b, h_kv, s, d);
-  check_strided_view(o, "o", b, h, s, d);
-  if (h_kv == h) check_same_strides(q, k, "q and k");
-  check_same_strides(k, v, "k and v");
-  if (kstart.has_value())
-    check_kstart(*kstart, c10::nullopt, false, q, causal, 0.0,
-                 klens.has_value(), check_values);
-  const int* klp = checked_klens(klens, causal, b);
-  long qs[3], os[3];
-  strides3(q, qs);
-  strides3(o, os);
-  auto lse = at::empty({b, h, s}, q.options().dtype(at::kFloat));
-  if (h_kv != h) {
-    long kvs[3];
-    strides3(k, kvs);
-    fs_flash_attn_fwd_v3_gqa(
-        q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-        lse.data_ptr<float>(),
-        kstart.has_value() ? kstart->data_ptr<int>() : nullptr, qs, kvs, os,
-        b, h, h_kv, s, d, (float)scale, cur_stream());
-    return lse;
+  const int h_kv = checked_kv_heads(k, h, causal, drop_p, klens.has_value());
+  // checks t as a [b, heads, s, d] operand, writes its strides to st3 (if
+  // given) and returns its address
+  auto operand = [&](const at::Tensor& t, const char* name, int heads,
+                     long* st3) {
+    long st[3] = {(long)heads * s * d, (long)s * d, (long)d};
+    if (contiguous) {
+      check_bf16_bhsd(t, name, b, heads, s, d);
+      TORCH_CHECK(t.is_contiguous(), name, ": must be contiguous");
+      TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
+                  ": base address must be 16-byte aligned");
+    } else {
+      check_strided_view(t, name, b, heads, s, d);
+      strides3(t, st);
+    }
+    if (st3) std::copy(st, st + 3, st3);
+    return t.data_ptr();
+  };
+  FlashV3Args a = {};
+  a.q = operand(q, "q", h, a.qs);
+  a.k = operand(k, "k", h_kv, a.kvs);
+  a.v = operand(v, "v", h_kv, nullptr);
+  a.o = operand(o, "o", h, a.os);
+  // k|v (and dk|dv) share one stride triple; with h_kv == h it is q's (dq's)
+  if (!contiguous) {
+    if (h_kv == h) check_same_strides(q, k, "q and k");
+    check_same_strides(k, v, "k and v");
+  }
+  if (g) {
+    a.dout = operand(g->dout, "dout", h, a.dos);
+    a.dq = operand(g->dq, "dq", h, a.gs);
+    a.dk = operand(g->dk, "dk", h_kv, a.gkvs);
+    a.dv = operand(g->dv, "dv", h_kv, nullptr);
+    if (!contiguous) {
+      if (h_kv == h) check_same_strides(g->dq, g->dk, "dq and dk");
+      check_same_strides(g->dk, g->dv, "dk and dv");
+    }
+    TORCH_CHECK(g->lse.is_cuda() && g->lse.scalar_type() == at::kFloat &&
+                    g->lse.is_contiguous() &&
+                    g->lse.numel() == (int64_t)b * h * s,
+                "lse must be contiguous fp32 [b, h, s]");
+    a.lse = g->lse.data_ptr<float>();
   }
   if (kstart.has_value()) {
-    fs_flash_attn_fwd_v3_kstart(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                                o.data_ptr(), lse.data_ptr<float>(),
-                                kstart->data_ptr<int>(), qs, os, b, h, s, d,
-                                (float)scale, cur_stream());
-    return lse;
+    check_kstart(*kstart, qend, g != nullptr, q, causal, drop_p,
+                 klens.has_value(), check_values);
+    a.kstart = kstart->data_ptr<int>();
+    a.qend = g ? qend->data_ptr<int>() : nullptr;
+  } else {
+    TORCH_CHECK(!qend.has_value(), "flash v3: qend without kstart");
   }
-  fs_flash_attn_fwd_v3_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                               o.data_ptr(), lse.data_ptr<float>(), klp, qs,
-                               os, b, h, s, d, causal ? 1 : 0, (float)scale,
-                               0.f, 0ull, cur_stream());
+  a.klens = checked_klens(klens, causal, b);
+  a.b = b, a.h = h, a.h_kv = h_kv, a.s = s, a.d = d;
+  a.causal = causal ? 1 : 0;
+  a.scale = (float)scale;
+  a.drop_p = (float)drop_p;
+  a.seed = (unsigned long long)seed;
+  return a;
+}
+
+// fp32 [b, h, s]: lse and the backward's delta scratch
+static at::Tensor new_lse(const at::Tensor& q) {
+  return at::empty({q.size(0), q.size(1), q.size(2)},
+                   q.options().dtype(at::kFloat));
+}
+
+// Contiguous [b, h, s, d] operands (k, v: [b, h_kv, s, d]); returns (o, lse).
+static std::vector<at::Tensor> flash_attn_fwd_v3(
+    at::Tensor q, at::Tensor k, at::Tensor v, double scale, bool causal,
+    c10::optional<at::Tensor> klens, double drop_p, int64_t seed,
+    c10::optional<at::Tensor> kstart, bool check_values) {
+  auto o = at::empty_like(q);
+  FlashV3Args a =
+      checked_flash_v3(q, k, v, o, nullptr, true, scale, causal, klens,
+                       drop_p, seed, kstart, c10::nullopt, check_values);
+  auto lse = new_lse(q);
+  a.lse = lse.data_ptr<float>();
+  fs_flash_v3_fwd(&a, cur_stream());
+  return {o, lse};
+}
+
+// Returns (dq, dk, dv), contiguous.
+static std::vector<at::Tensor> flash_attn_bwd_v3(
+    at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor dout,
+    at::Tensor lse, double scale, bool causal,
+    c10::optional<at::Tensor> klens, double drop_p, int64_t seed,
+    c10::optional<at::Tensor> kstart, c10::optional<at::Tensor> qend,
+    bool check_values) {
+  dout = dout.contiguous();
+  auto dq = at::empty_like(q), dk = at::empty_like(k), dv = at::empty_like(v);
+  const FlashV3Grads g{dout, lse, dq, dk, dv};
+  FlashV3Args a =
+      checked_flash_v3(q, k, v, o, &g, true, scale, causal, klens, drop_p,
+                       seed, kstart, qend, check_values);
+  auto delta = new_lse(q);
+  a.delta_ws = delta.data_ptr<float>();
+  fs_flash_v3_bwd(&a, cur_stream());
+  return {dq, dk, dv};
+}
+
+// Writes o in place; returns lse [b, h, s] fp32.  No dropout.
+static at::Tensor flash_attn_fwd_v3_strided(
+    at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, double scale,
+    bool causal, c10::optional<at::Tensor> klens,
+    c10::optional<at::Tensor> kstart, bool check_values) {
+  FlashV3Args a =
+      checked_flash_v3(q, k, v, o, nullptr, false, scale, causal, klens, 0.0,
+                       0, kstart, c10::nullopt, check_values);
+  auto lse = new_lse(q);
+  a.lse = lse.data_ptr<float>();
+  fs_flash_v3_fwd(&a, cur_stream());
   return lse;
 }
 
@@ -692,68 +751,13 @@ static void flash_attn_bwd_v3_strided(
     bool causal, c10::optional<at::Tensor> klens,
     c10::optional<at::Tensor> kstart, c10::optional<at::Tensor> qend,
     bool check_values) {
-  TORCH_CHECK(q.dim() == 4, "q must be [b, h, s, d]");
-  const int b = q.size(0), h = q.size(1), s = q.size(2), d = q.size(3);
-  TORCH_CHECK((d == 128 || d == 96 || d == 64) && s % 64 == 0 && s >= 64,
-              "flash v3: d in {64, 96, 128}, s a multiple of 64");
-  const int h_kv = checked_kv_heads(k, h, causal, 0.0, klens.has_value());
-  check_strided_view(q, "q", b, h, s, d);
-  check_strided_view(k, "k", b, h_kv, s, d);
-  check_strided_view(v, "v", b, h_kv, s, d);
-  check_strided_view(o, "o", b, h, s, d);
-  check_strided_view(dout, "dout", b, h, s, d);
-  check_strided_view(dq, "dq", b, h, s, d);
-  check_strided_view(dk, "dk", b, h_kv, s, d);
-  check_strided_view(dv, "dv", b, h_kv, s, d);
-  if (h_kv == h) {
-    check_same_strides(q, k, "q and k");
-    check_same_strides(dq, dk, "dq and dk");
-  }
-  check_same_strides(k, v, "k and v");
-  check_same_strides(dk, dv, "dk and dv");
-  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat &&
-              lse.is_contiguous() && lse.numel() == (int64_t)b * h * s,
-              "lse must be contiguous fp32 [b, h, s]");
-  if (kstart.has_value())
-    check_kstart(*kstart, qend, true, q, causal, 0.0, klens.has_value(),
-                 check_values);
-  else
-    TORCH_CHECK(!qend.has_value(), "flash v3: qend without kstart");
-  const int* klp = checked_klens(klens, causal, b);
-  long qs[3], os[3], dos[3], gs[3];
-  strides3(q, qs);
-  strides3(o, os);
-  strides3(dout, dos);
-  strides3(dq, gs);
-  auto delta = at::empty({b, h, s}, q.options().dtype(at::kFloat));
-  if (h_kv != h) {
-    long kvs[3], gkvs[3];
-    strides3(k, kvs);
-    strides3(dk, gkvs);
-    const bool ks = kstart.has_value();
-    fs_flash_attn_bwd_v3_gqa(
-        q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-        dout.data_ptr(), lse.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(),
-        dv.data_ptr(), delta.data_ptr<float>(),
-        ks ? kstart->data_ptr<int>() : nullptr,
-        ks ? qend->data_ptr<int>() : nullptr, qs, kvs, os, dos, gs, gkvs, b,
-        h, h_kv, s, d, (float)scale, cur_stream());
-    return;
-  }
-  if (kstart.has_value()) {
-    fs_flash_attn_bwd_v3_kstart(
-        q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-        dout.data_ptr(), lse.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(),
-        dv.data_ptr(), delta.data_ptr<float>(), kstart->data_ptr<int>(),
-        qend->data_ptr<int>(), qs, os, dos, gs, b, h, s, d, (float)scale,
-        cur_stream());
-    return;
-  }
-  fs_flash_attn_bwd_v3_strided(
-      q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(),
-      lse.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
-      delta.data_ptr<float>(), klp, qs, os, dos, gs, b, h, s, d,
-      causal ? 1 : 0, (float)scale, 0.f, 0ull, cur_stream());
+  const FlashV3Grads g{dout, lse, dq, dk, dv};
+  FlashV3Args a =
+      checked_flash_v3(q, k, v, o, &g, false, scale, causal, klens, 0.0, 0,
+                       kstart, qend, check_values);
+  auto delta = new_lse(q);
+  a.delta_ws = delta.data_ptr<float>();
+  fs_flash_v3_bwd(&a, cur_stream());
 }
 
 // Host only: row L of the int32 [nx * ny * nz, 3] result is the logical
@@ -777,6 +781,20 @@ static at::Tensor flash_v3_block_map(int64_t nx, int64_t ny, int64_t nz,
   return out;
 }
 
+// cos/sin tables of the in-place rotary: contiguous fp32 [S, hn] on the GPU
+// with S >= offset + s.
+static void check_rope_tables(const at::Tensor& cos, const at::Tensor& sin,
+                              int64_t offset, int s, int hn) {
+  TORCH_CHECK(cos.is_cuda() && sin.is_cuda() &&
+              cos.scalar_type() == at::kFloat &&
+              sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
+              sin.is_contiguous() && cos.dim() == 2 && cos.size(1) == hn &&
+              sin.sizes() == cos.sizes(),
+              "cos/sin must be contiguous fp32 [S, hn]");
+  TORCH_CHECK(offset >= 0 && offset + s <= cos.size(0),
+              "rope table too short for offset + s");
+}
+
 // Rotates q and k ([b, np, s, hn] views sharing strides) in place;
 // bwd = transpose rotation for gradients.  cos/sin: [S, hn] fp32.
 static void rope_inplace(at::Tensor q, at::Tensor k, at::Tensor cos,
@@ -788,14 +806,7 @@ static void rope_inplace(at::Tensor q, at::Tensor k, at::Tensor cos,
   check_strided_view(q, "q", b, np, s, hn);
   check_strided_view(k, "k", b, np, s, hn);
   check_same_strides(q, k, "q and k");
-  TORCH_CHECK(cos.is_cuda() && sin.is_cuda() &&
-              cos.scalar_type() == at::kFloat &&
-              sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
-              sin.is_contiguous() && cos.dim() == 2 && cos.size(1) == hn &&
-              sin.sizes() == cos.sizes(),
-              "cos/sin must be contiguous fp32 [S, hn]");
-  TORCH_CHECK(offset >= 0 && offset + s <= cos.size(0),
-              "rope table too short for offset + s");
+  check_rope_tables(cos, sin, offset, s, hn);
   fs_rope_inplace(q.data_ptr(), k.data_ptr(), cos.data_ptr<float>(),
                   sin.data_ptr<float>(), b, np, s, hn, q.stride(0),
                   q.stride(1), q.stride(2), (int)offset, bwd ? 1 : 0,
@@ -811,14 +822,7 @@ static void rope_inplace_one(at::Tensor x, at::Tensor cos, at::Tensor sin,
   TORCH_CHECK((hn / 2) % 8 == 0 && hn % 2 == 0,
               "head_dim/2 must be divisible by 8");
   check_strided_view(x, "x", b, np, s, hn);
-  TORCH_CHECK(cos.is_cuda() && sin.is_cuda() &&
-              cos.scalar_type() == at::kFloat &&
-              sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
-              sin.is_contiguous() && cos.dim() == 2 && cos.size(1) == hn &&
-              sin.sizes() == cos.sizes(),
-              "cos/sin must be contiguous fp32 [S, hn]");
-  TORCH_CHECK(offset >= 0 && offset + s <= cos.size(0),
-              "rope table too short for offset + s");
+  check_rope_tables(cos, sin, offset, s, hn);
   fs_rope_inplace(x.data_ptr(), nullptr, cos.data_ptr<float>(),
                   sin.data_ptr<float>(), b, np, s, hn, x.stride(0),
                   x.stride(1), x.stride(2), (int)offset, bwd ? 1 : 0,
@@ -1148,85 +1152,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
                     (int)vstart, (int)vend, cur_stream());
     return dl;
   });
-  mod.def("flash_attn_bwd_v3", [](at::Tensor q, at::Tensor k, at::Tensor v,
-                                  at::Tensor o, at::Tensor dout,
-                                  at::Tensor lse, double scale, bool causal,
-                                  c10::optional<at::Tensor> klens,
-                                  double drop_p, int64_t seed,
-                                  c10::optional<at::Tensor> kstart,
-                                  c10::optional<at::Tensor> qend,
-                                  bool check_values) {
-    const int b = q.size(0), h = q.size(1), s = q.size(2), d = q.size(3);
-    TORCH_CHECK((d == 128 || d == 96 || d == 64) && s % 64 == 0);
-    const bool gqa =
-        checked_kv_heads(k, h, causal, drop_p, klens.has_value()) != h;
-    if (kstart.has_value() || gqa) {
-      // the kstart and GQA kernels have one (strided) entry; contiguous
-      // operands are its special case and get all of its checks
-      TORCH_CHECK(drop_p == 0.0, "flash v3: kstart does not support dropout");
-      TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous());
-      auto dq = at::empty_like(q);
-      auto dk = at::empty_like(k);
-      auto dv = at::empty_like(v);
-      flash_attn_bwd_v3_strided(q, k, v, o, dout.contiguous(), lse, dq, dk,
-                                dv, scale, causal, klens, kstart, qend,
-                                check_values);
-      return std::vector<at::Tensor>{dq, dk, dv};
-    }
-    TORCH_CHECK(!qend.has_value(), "flash v3: qend without kstart");
-    const int* klp = nullptr;
-    if (klens.has_value()) klp = klens->data_ptr<int>();
-    auto dq = at::empty_like(q);
-    auto dk = at::empty_like(k);
-    auto dv = at::empty_like(v);
-    auto delta = at::empty({b, h, s}, q.options().dtype(at::kFloat));
-    fs_flash_attn_bwd_v3(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                         o.data_ptr(), dout.contiguous().data_ptr(),
-                         lse.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(),
-                         dv.data_ptr(), delta.data_ptr<float>(), klp, b, h,
-                         s, d, causal ? 1 : 0, (float)scale, (float)drop_p,
-                         (unsigned long long)seed, cur_stream());
-    return std::vector<at::Tensor>{dq, dk, dv};
-  }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("dout"),
-     py::arg("lse"), py::arg("scale"), py::arg("causal"), py::arg("klens"),
-     py::arg("drop_p"), py::arg("seed"), py::arg("kstart") = py::none(),
-     py::arg("qend") = py::none(), py::arg("check_values") = false);
-  mod.def("flash_attn_fwd_v3", [](at::Tensor q, at::Tensor k, at::Tensor v,
-                                  double scale, bool causal,
-                                  c10::optional<at::Tensor> klens,
-                                  double drop_p, int64_t seed,
-                                  c10::optional<at::Tensor> kstart,
-                                  bool check_values) {
-    TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous());
-    TORCH_CHECK(q.scalar_type() == at::kBFloat16);
-    const int b = q.size(0), h = q.size(1), s = q.size(2), d = q.size(3);
-    TORCH_CHECK((d == 128 || d == 96 || d == 64) && s % 64 == 0 && s >= 64);
-    TORCH_CHECK(k.size(2) == s, "v3 is self-attention (sq == sk)");
-    const bool gqa =
-        checked_kv_heads(k, h, causal, drop_p, klens.has_value()) != h;
-    if (kstart.has_value() || gqa) {
-      TORCH_CHECK(drop_p == 0.0, "flash v3: kstart does not support dropout");
-      auto o = at::empty_like(q);
-      auto lse = flash_attn_fwd_v3_strided(q, k, v, o, scale, causal, klens,
-                                           kstart, check_values);
-      return std::vector<at::Tensor>{o, lse};
-    }
-    const int* klp = nullptr;
-    if (klens.has_value()) {
-      TORCH_CHECK(klens->scalar_type() == at::kInt
-                  && klens->numel() == b && klens->is_contiguous());
-      klp = klens->data_ptr<int>();
-    }
-    auto o = at::empty_like(q);
-    auto lse = at::empty({b, h, s}, q.options().dtype(at::kFloat));
-    fs_flash_attn_fwd_v3(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                         o.data_ptr(), lse.data_ptr<float>(), klp, b, h, s,
-                         d, causal ? 1 : 0, (float)scale, (float)drop_p,
-                         (unsigned long long)seed, cur_stream());
-    return std::vector<at::Tensor>{o, lse};
-  }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
-     py::arg("causal"), py::arg("klens"), py::arg("drop_p"), py::arg("seed"),
-     py::arg("kstart") = py::none(), py::arg("check_values") = false);
+  mod.def("flash_attn_fwd_v3", &flash_attn_fwd_v3, py::arg("q"), py::arg("k"),
+          py::arg("v"), py::arg("scale"), py::arg("causal"), py::arg("klens"),
+          py::arg("drop_p"), py::arg("seed"), py::arg("kstart") = py::none(),
+          py::arg("check_values") = false);
+  mod.def("flash_attn_bwd_v3", &flash_attn_bwd_v3, py::arg("q"), py::arg("k"),
+          py::arg("v"), py::arg("o"), py::arg("dout"), py::arg("lse"),
+          py::arg("scale"), py::arg("causal"), py::arg("klens"),
+          py::arg("drop_p"), py::arg("seed"), py::arg("kstart") = py::none(),
+          py::arg("qend") = py::none(), py::arg("check_values") = false);
   mod.def("flash_attn_bwd", &flash_attn_bwd);
   mod.def("flash_attn_fwd_v3_strided", &flash_attn_fwd_v3_strided,
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),

@@ -30,6 +30,7 @@
 
 #include "common.h"
 #include "flash_blockmap.h"
+#include "flash_v3.h"
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -1489,101 +1490,80 @@ void flash_attn_fwd_v3_kernel(const bf16_t* __restrict__ Q,
   }
 }
 
-// qs3 / os3: (batch, head, row) element strides of q|k|v and of o.
-extern "C" void fs_flash_attn_fwd_v3_strided(
-    const void* q, const void* k, const void* v, void* o, float* lse,
-    const int* klens, const long* qs3, const long* os3, int b, int h, int s,
-    int d, int causal, float scale, float drop_p, unsigned long long seed,
-    hipStream_t stream) {
-  const FaStrides qs{qs3[0], qs3[1], qs3[2]};
-  const FaStrides os{os3[0], os3[1], os3[2]};
-  dim3 grid((s + V3_QBLK - 1) / V3_QBLK, h, b);
-  dim3 block(FA_WAVES * 64);
-  const unsigned int dth =
-      (drop_p > 0.f) ? (unsigned int)(drop_p * 4294967296.0) : 0u;
-  const float ksc = (drop_p > 0.f) ? 1.f / (1.f - drop_p) : 1.f;
-#define V3F(DD, CC, DR) hipLaunchKernelGGL( \
-    (flash_attn_fwd_v3_kernel<DD, CC, DR>), \
-    grid, block, 0, stream, (const bf16_t*)q, (const bf16_t*)k, \
-    (const bf16_t*)v, (bf16_t*)o, lse, klens, qs, os, b, h, s, scale, dth, \
-    ksc, seed, (const int*)nullptr, FaStrides{}, 1)
-  if (dth) {
-    if (d == 128 && causal) V3F(128, true, true);
-    else if (d == 128) V3F(128, false, true);
-    else if (d == 96 && causal) V3F(96, true, true);
-    else if (d == 96) V3F(96, false, true);
-    else if (d == 64 && causal) V3F(64, true, true);
-    else V3F(64, false, true);
-  } else {
-    if (d == 128 && causal) V3F(128, true, false);
-    else if (d == 128) V3F(128, false, false);
-    else if (d == 96 && causal) V3F(96, true, false);
-    else if (d == 96) V3F(96, false, false);
-    else if (d == 64 && causal) V3F(64, true, false);
-    else V3F(64, false, false);
+// ---- host side of v3: FlashV3Args (flash_v3.h) -> one kernel variant -----
+static FaStrides v3_strides(const long* s3) {
+  return FaStrides{s3[0], s3[1], s3[2]};
+}
+
+// Dropout threshold on the 32-bit hash and the keep scale.  Forward and
+// backward must agree on both bit for bit, so both take them from here.
+struct V3Drop {
+  unsigned int dth;
+  float ksc;
+};
+
+static V3Drop v3_drop(float drop_p) {
+  if (!(drop_p > 0.f)) return {0u, 1.f};
+  return {(unsigned int)(drop_p * 4294967296.0), 1.f / (1.f - drop_p)};
+}
+
+// klens and the dropout arguments as the kernels get them: the kstart and
+// GQA variants take neither.
+struct V3Opts {
+  const int* klens;
+  V3Drop drop;
+  unsigned long long seed;
+};
+
+template <bool KS, bool GQA>
+static V3Opts v3_opts(const FlashV3Args& a) {
+  if (KS || GQA) return {nullptr, {0u, 1.f}, 0ull};
+  return {a.klens, v3_drop(a.drop_p), a.seed};
+}
+
+// The seven variants instantiated per head dim: <CAUSAL, HAS_DROP> in
+// {0,1}^2, kstart, and GQA with and without kstart (the last three causal
+// without dropout -- the bindings refuse anything else).  L is V3Fwd or
+// V3Bwd.
+template <class L, int D>
+static void v3_variant(const FlashV3Args& a, hipStream_t stream) {
+  const bool gqa = a.h_kv != a.h, ks = a.kstart != nullptr;
+  const bool drop = v3_drop(a.drop_p).dth != 0;
+#define V3_RUN(...) L::template run<D, __VA_ARGS__>(a, stream)
+  if (gqa && ks) V3_RUN(true, false, true, true);
+  else if (gqa) V3_RUN(true, false, false, true);
+  else if (ks) V3_RUN(true, false, true, false);
+  else if (a.causal && drop) V3_RUN(true, true, false, false);
+  else if (a.causal) V3_RUN(true, false, false, false);
+  else if (drop) V3_RUN(false, true, false, false);
+  else V3_RUN(false, false, false, false);
+#undef V3_RUN
+}
+
+template <class L>
+static void v3_dispatch(const FlashV3Args& a, hipStream_t stream) {
+  if (a.d == 128) v3_variant<L, 128>(a, stream);
+  else if (a.d == 96) v3_variant<L, 96>(a, stream);
+  else v3_variant<L, 64>(a, stream);
+}
+
+struct V3Fwd {
+  template <int D, bool CAUSAL, bool HAS_DROP, bool KS, bool GQA>
+  static void run(const FlashV3Args& a, hipStream_t stream) {
+    const V3Opts opt = v3_opts<KS, GQA>(a);
+    hipLaunchKernelGGL(
+        (flash_attn_fwd_v3_kernel<D, CAUSAL, HAS_DROP, KS, GQA>),
+        dim3((a.s + V3_QBLK - 1) / V3_QBLK, a.h, a.b), dim3(FA_WAVES * 64), 0,
+        stream, (const bf16_t*)a.q, (const bf16_t*)a.k, (const bf16_t*)a.v,
+        (bf16_t*)a.o, a.lse, opt.klens, v3_strides(a.qs), v3_strides(a.os),
+        a.b, a.h, a.s, a.scale, opt.drop.dth, opt.drop.ksc, opt.seed,
+        a.kstart, GQA ? v3_strides(a.kvs) : FaStrides{},
+        GQA ? a.h / a.h_kv : 1);
   }
-#undef V3F
-}
+};
 
-// Causal forward with a per-row key start (kstart [b, s] int32, see
-// v3_kstart_at); no dropout, no klens.
-extern "C" void fs_flash_attn_fwd_v3_kstart(
-    const void* q, const void* k, const void* v, void* o, float* lse,
-    const int* kstart, const long* qs3, const long* os3, int b, int h, int s,
-    int d, float scale, hipStream_t stream) {
-  const FaStrides qs{qs3[0], qs3[1], qs3[2]};
-  const FaStrides os{os3[0], os3[1], os3[2]};
-  dim3 grid((s + V3_QBLK - 1) / V3_QBLK, h, b);
-  dim3 block(FA_WAVES * 64);
-#define V3K(DD) hipLaunchKernelGGL( \
-    (flash_attn_fwd_v3_kernel<DD, true, false, true>), \
-    grid, block, 0, stream, (const bf16_t*)q, (const bf16_t*)k, \
-    (const bf16_t*)v, (bf16_t*)o, lse, (const int*)nullptr, qs, os, b, h, s, \
-    scale, 0u, 1.f, 0ull, kstart, FaStrides{}, 1)
-  if (d == 128) V3K(128);
-  else if (d == 96) V3K(96);
-  else V3K(64);
-#undef V3K
-}
-
-// Grouped-query causal forward: q/o have h heads, k/v h_kv = h / G heads
-// with strides kvs3 of their own; query head j reads KV head j / G.
-// kstart may be null.  No dropout, no klens.
-extern "C" void fs_flash_attn_fwd_v3_gqa(
-    const void* q, const void* k, const void* v, void* o, float* lse,
-    const int* kstart, const long* qs3, const long* kvs3, const long* os3,
-    int b, int h, int h_kv, int s, int d, float scale, hipStream_t stream) {
-  const FaStrides qs{qs3[0], qs3[1], qs3[2]};
-  const FaStrides kvs{kvs3[0], kvs3[1], kvs3[2]};
-  const FaStrides os{os3[0], os3[1], os3[2]};
-  dim3 grid((s + V3_QBLK - 1) / V3_QBLK, h, b);
-  dim3 block(FA_WAVES * 64);
-#define V3G(DD, KK) hipLaunchKernelGGL( \
-    (flash_attn_fwd_v3_kernel<DD, true, false, KK, true>), \
-    grid, block, 0, stream, (const bf16_t*)q, (const bf16_t*)k, \
-    (const bf16_t*)v, (bf16_t*)o, lse, (const int*)nullptr, qs, os, b, h, s, \
-    scale, 0u, 1.f, 0ull, kstart, kvs, h / h_kv)
-  if (kstart) {
-    if (d == 128) V3G(128, true);
-    else if (d == 96) V3G(96, true);
-    else V3G(64, true);
-  } else {
-    if (d == 128) V3G(128, false);
-    else if (d == 96) V3G(96, false);
-    else V3G(64, false);
-  }
-#undef V3G
-}
-
-extern "C" void fs_flash_attn_fwd_v3(const void* q, const void* k,
-                                     const void* v, void* o, float* lse,
-                                     const int* klens, int b, int h, int s,
-                                     int d, int causal, float scale,
-                                     float drop_p, unsigned long long seed,
-                                     hipStream_t stream) {
-  const long c3[3] = {(long)h * s * d, (long)s * d, (long)d};
-  fs_flash_attn_fwd_v3_strided(q, k, v, o, lse, klens, c3, c3, b, h, s, d,
-                               causal, scale, drop_p, seed, stream);
+extern "C" void fs_flash_v3_fwd(const FlashV3Args* a, hipStream_t stream) {
+  v3_dispatch<V3Fwd>(*a, stream);
 }
 
 // ===========================================================================
@@ -2085,170 +2065,47 @@ void flash_attn_bwd_dkv_v3_kernel(const bf16_t* __restrict__ Q,
   }
 }
 
-template <int D, bool CAUSAL, bool HAS_DROP, bool KS = false>
-static void launch_bwd_v3(const void* q, const void* k, const void* v,
-                          const void* o, const void* dout, const float* lse,
-                          void* dq, void* dk, void* dv, float* delta_ws,
-                          const int* klens, FaStrides qs, FaStrides os,
-                          FaStrides dos, FaStrides gs, int b, int h, int s,
-                          float scale, unsigned int dth, float ksc,
-                          unsigned long long seed, hipStream_t stream,
-                          const int* kstart = nullptr,
-                          const int* qend = nullptr) {
-  {
+// delta and dq run per query head (grid y = h), dkv per KV head (grid
+// y = h_kv, the group loop inside the block).  delta does not depend on the
+// mask, so flash_delta_v3_kernel serves every variant.
+struct V3Bwd {
+  template <int D, bool CAUSAL, bool HAS_DROP, bool KS, bool GQA>
+  static void run(const FlashV3Args& a, hipStream_t stream) {
+    const V3Opts opt = v3_opts<KS, GQA>(a);
+    const FaStrides qs = v3_strides(a.qs), dos = v3_strides(a.dos);
+    const FaStrides gs = v3_strides(a.gs);
+    const FaStrides kvs = GQA ? v3_strides(a.kvs) : FaStrides{};
+    const FaStrides gkvs = GQA ? v3_strides(a.gkvs) : FaStrides{};
+    const int G = GQA ? a.h / a.h_kv : 1;
+    const bf16_t* q = (const bf16_t*)a.q;
+    const bf16_t* k = (const bf16_t*)a.k;
+    const bf16_t* v = (const bf16_t*)a.v;
+    const bf16_t* dout = (const bf16_t*)a.dout;
     // at most 16 x-blocks per (batch, head): plenty of blocks to fill the
     // chip while each wave still streams several rows
-    int bx = (s + 31) / 32;
+    int bx = (a.s + 31) / 32;
     if (bx > 16) bx = 16;
-    hipLaunchKernelGGL((flash_delta_v3_kernel<D>), dim3(bx, h, b), dim3(256),
-                       0, stream, (const bf16_t*)dout, (const bf16_t*)o,
-                       delta_ws, dos, os, h, s);
+    hipLaunchKernelGGL((flash_delta_v3_kernel<D>), dim3(bx, a.h, a.b),
+                       dim3(256), 0, stream, dout, (const bf16_t*)a.o,
+                       a.delta_ws, dos, v3_strides(a.os), a.h, a.s);
+    const int nx = (a.s + V3_QBLK - 1) / V3_QBLK;
+    const dim3 block(FA_WAVES * 64);
+    hipLaunchKernelGGL(
+        (flash_attn_bwd_dq_v3_kernel<D, CAUSAL, HAS_DROP, KS, GQA>),
+        dim3(nx, a.h, a.b), block, 0, stream, q, k, v, dout,
+        a.lse, a.delta_ws, (bf16_t*)a.dq,
+        opt.klens, qs, dos, gs, a.b, a.h, a.s, a.scale, opt.drop.dth,
+        opt.drop.ksc, opt.seed, a.kstart, kvs, G);
+    hipLaunchKernelGGL(
+        (flash_attn_bwd_dkv_v3_kernel<D, CAUSAL, HAS_DROP, KS, GQA>),
+        dim3(nx, a.h_kv, a.b), block, 0, stream, q, k, v, dout,
+        a.lse, a.delta_ws, (bf16_t*)a.dk,
+        (bf16_t*)a.dv, opt.klens, qs, dos, gs, a.b, a.h, a.s, a.scale,
+        opt.drop.dth, opt.drop.ksc, opt.seed, a.kstart, a.qend, kvs, gkvs, G);
   }
-  dim3 grid((s + V3_QBLK - 1) / V3_QBLK, h, b);
-  dim3 block(FA_WAVES * 64);
-  hipLaunchKernelGGL((flash_attn_bwd_dq_v3_kernel<D, CAUSAL, HAS_DROP, KS>),
-                     grid, block, 0, stream, (const bf16_t*)q,
-                     (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout,
-                     lse, delta_ws, (bf16_t*)dq, klens, qs, dos, gs, b, h, s,
-                     scale, dth, ksc, seed, kstart, FaStrides{}, 1);
-  hipLaunchKernelGGL((flash_attn_bwd_dkv_v3_kernel<D, CAUSAL, HAS_DROP, KS>),
-                     grid, block, 0, stream, (const bf16_t*)q,
-                     (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout,
-                     lse, delta_ws, (bf16_t*)dk, (bf16_t*)dv, klens, qs, dos,
-                     gs, b, h, s, scale, dth, ksc, seed, kstart, qend,
-                     FaStrides{}, FaStrides{}, 1);
+};
+
+extern "C" void fs_flash_v3_bwd(const FlashV3Args* a, hipStream_t stream) {
+  v3_dispatch<V3Bwd>(*a, stream);
 }
 
-// Grouped-query backward: delta and dq run per query head (grid y = h), dkv
-// per KV head (grid y = h_kv) with the group loop inside the block.
-template <int D, bool KS>
-static void launch_bwd_v3_gqa(const void* q, const void* k, const void* v,
-                              const void* o, const void* dout,
-                              const float* lse, void* dq, void* dk, void* dv,
-                              float* delta_ws, FaStrides qs, FaStrides kvs,
-                              FaStrides os, FaStrides dos, FaStrides gs,
-                              FaStrides gkvs, int b, int h, int h_kv, int s,
-                              float scale, hipStream_t stream,
-                              const int* kstart, const int* qend) {
-  int bx = (s + 31) / 32;
-  if (bx > 16) bx = 16;
-  hipLaunchKernelGGL((flash_delta_v3_kernel<D>), dim3(bx, h, b), dim3(256),
-                     0, stream, (const bf16_t*)dout, (const bf16_t*)o,
-                     delta_ws, dos, os, h, s);
-  const int G = h / h_kv;
-  const int nx = (s + V3_QBLK - 1) / V3_QBLK;
-  dim3 block(FA_WAVES * 64);
-  hipLaunchKernelGGL(
-      (flash_attn_bwd_dq_v3_kernel<D, true, false, KS, true>), dim3(nx, h, b),
-      block, 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
-      (const bf16_t*)dout, lse, delta_ws, (bf16_t*)dq, (const int*)nullptr,
-      qs, dos, gs, b, h, s, scale, 0u, 1.f, 0ull, kstart, kvs, G);
-  hipLaunchKernelGGL(
-      (flash_attn_bwd_dkv_v3_kernel<D, true, false, KS, true>),
-      dim3(nx, h_kv, b), block, 0, stream, (const bf16_t*)q, (const bf16_t*)k,
-      (const bf16_t*)v, (const bf16_t*)dout, lse, delta_ws, (bf16_t*)dk,
-      (bf16_t*)dv, (const int*)nullptr, qs, dos, gs, b, h, s, scale, 0u, 1.f,
-      0ull, kstart, qend, kvs, gkvs, G);
-}
-
-// qs3: q|k|v, os3: o, dos3: dout, gs3: dq|dk|dv (batch, head, row) strides.
-extern "C" void fs_flash_attn_bwd_v3_strided(
-    const void* q, const void* k, const void* v, const void* o,
-    const void* dout, const float* lse, void* dq, void* dk, void* dv,
-    float* delta_ws, const int* klens, const long* qs3, const long* os3,
-    const long* dos3, const long* gs3, int b, int h, int s, int d,
-    int causal, float scale, float drop_p, unsigned long long seed,
-    hipStream_t stream) {
-  const FaStrides qs{qs3[0], qs3[1], qs3[2]};
-  const FaStrides os{os3[0], os3[1], os3[2]};
-  const FaStrides dos{dos3[0], dos3[1], dos3[2]};
-  const FaStrides gs{gs3[0], gs3[1], gs3[2]};
-  const unsigned int dth =
-      (drop_p > 0.f) ? (unsigned int)(drop_p * 4294967296.0) : 0u;
-  const float ksc = (drop_p > 0.f) ? 1.f / (1.f - drop_p) : 1.f;
-#define BWD3(DD, CC, DR) launch_bwd_v3<DD, CC, DR>( \
-      q, k, v, o, dout, lse, dq, dk, dv, delta_ws, klens, qs, os, dos, gs, \
-      b, h, s, scale, dth, ksc, seed, stream)
-  if (dth) {
-    if (d == 128 && causal) BWD3(128, true, true);
-    else if (d == 128) BWD3(128, false, true);
-    else if (d == 96 && causal) BWD3(96, true, true);
-    else if (d == 96) BWD3(96, false, true);
-    else if (d == 64 && causal) BWD3(64, true, true);
-    else BWD3(64, false, true);
-  } else {
-    if (d == 128 && causal) BWD3(128, true, false);
-    else if (d == 128) BWD3(128, false, false);
-    else if (d == 96 && causal) BWD3(96, true, false);
-    else if (d == 96) BWD3(96, false, false);
-    else if (d == 64 && causal) BWD3(64, true, false);
-    else BWD3(64, false, false);
-  }
-#undef BWD3
-}
-
-// Causal backward with a per-row key start; qend [b, s/64] int32 is the
-// query-loop bound of dkv (see flash_attn_bwd_dkv_v3_kernel).  delta does
-// not depend on the mask, so flash_delta_v3_kernel serves both.
-extern "C" void fs_flash_attn_bwd_v3_kstart(
-    const void* q, const void* k, const void* v, const void* o,
-    const void* dout, const float* lse, void* dq, void* dk, void* dv,
-    float* delta_ws, const int* kstart, const int* qend, const long* qs3,
-    const long* os3, const long* dos3, const long* gs3, int b, int h, int s,
-    int d, float scale, hipStream_t stream) {
-  const FaStrides qs{qs3[0], qs3[1], qs3[2]};
-  const FaStrides os{os3[0], os3[1], os3[2]};
-  const FaStrides dos{dos3[0], dos3[1], dos3[2]};
-  const FaStrides gs{gs3[0], gs3[1], gs3[2]};
-#define BWD3K(DD) launch_bwd_v3<DD, true, false, true>( \
-      q, k, v, o, dout, lse, dq, dk, dv, delta_ws, nullptr, qs, os, dos, gs, \
-      b, h, s, scale, 0u, 1.f, 0ull, stream, kstart, qend)
-  if (d == 128) BWD3K(128);
-  else if (d == 96) BWD3K(96);
-  else BWD3K(64);
-#undef BWD3K
-}
-
-// kvs3: k|v, gkvs3: dk|dv strides; kstart / qend both null or both set.
-extern "C" void fs_flash_attn_bwd_v3_gqa(
-    const void* q, const void* k, const void* v, const void* o,
-    const void* dout, const float* lse, void* dq, void* dk, void* dv,
-    float* delta_ws, const int* kstart, const int* qend, const long* qs3,
-    const long* kvs3, const long* os3, const long* dos3, const long* gs3,
-    const long* gkvs3, int b, int h, int h_kv, int s, int d, float scale,
-    hipStream_t stream) {
-  const FaStrides qs{qs3[0], qs3[1], qs3[2]};
-  const FaStrides kvs{kvs3[0], kvs3[1], kvs3[2]};
-  const FaStrides os{os3[0], os3[1], os3[2]};
-  const FaStrides dos{dos3[0], dos3[1], dos3[2]};
-  const FaStrides gs{gs3[0], gs3[1], gs3[2]};
-  const FaStrides gkvs{gkvs3[0], gkvs3[1], gkvs3[2]};
-#define BWD3G(DD, KK) launch_bwd_v3_gqa<DD, KK>( \
-      q, k, v, o, dout, lse, dq, dk, dv, delta_ws, qs, kvs, os, dos, gs, \
-      gkvs, b, h, h_kv, s, scale, stream, kstart, qend)
-  if (kstart) {
-    if (d == 128) BWD3G(128, true);
-    else if (d == 96) BWD3G(96, true);
-    else BWD3G(64, true);
-  } else {
-    if (d == 128) BWD3G(128, false);
-    else if (d == 96) BWD3G(96, false);
-    else BWD3G(64, false);
-  }
-#undef BWD3G
-}
-
-extern "C" void fs_flash_attn_bwd_v3(const void* q, const void* k,
-                                     const void* v, const void* o,
-                                     const void* dout, const float* lse,
-                                     void* dq, void* dk, void* dv,
-                                     float* delta_ws, const int* klens,
-                                     int b, int h, int s, int d, int causal,
-                                     float scale, float drop_p,
-                                     unsigned long long seed,
-                                     hipStream_t stream) {
-  const long c3[3] = {(long)h * s * d, (long)s * d, (long)d};
-  fs_flash_attn_bwd_v3_strided(q, k, v, o, dout, lse, dq, dk, dv, delta_ws,
-                               klens, c3, c3, c3, c3, b, h, s, d, causal,
-                               scale, drop_p, seed, stream);
-}

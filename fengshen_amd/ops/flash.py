@@ -32,7 +32,7 @@ _FLASH_DIMS = (40, 64, 80, 96, 128, 160)
 
 def _v3_eligible(ext, q, k, causal, klens, dropout_p):
     """v3 (swapped-QK^T 32x32 schedule, ~1.8x): self-attention at
-    d in {64, 128} with s % 64 == 0; causal or klens-masked bidirectional.
+    d in {64, 96, 128} with s % 64 == 0; causal or klens-masked bidirectional.
     Dropout routes to the general kernels by default: a same-box A/B on
     the BERT step (b128 s512 d64 p=0.1) measured them identical (177.2
     vs 177.5/178.8 samples/s — the step is no longer attention-bound),
@@ -190,19 +190,17 @@ class _FlashAttention(torch.autograd.Function):
     def forward(ctx, q, k, v, scale, causal, klens, dropout_p, seed,
                 kstart=None):
         ext = get_ext()
+        # The kernel family is chosen here, once, and kept on ctx: backward
+        # must read the lse of the family that wrote it.  kstart and
+        # grouped-query K/V exist in the v3 kernels only -- no quiet
+        # fall-back, the binding raises on what they do not cover.
+        ctx.v3 = (kstart is not None or k.shape[1] != q.shape[1]
+                  or _v3_eligible(ext, q, k, causal, klens, dropout_p))
         ctx.kstart = kstart
-        if kstart is not None:
-            # no quiet fall-back: the binding raises on anything the
-            # kstart kernels do not cover
+        ctx.qend = None if kstart is None else kstart_qend(kstart)
+        if ctx.v3:
             o, lse = ext.flash_attn_fwd_v3(q, k, v, scale, causal, klens,
                                            dropout_p, seed, kstart=kstart)
-            ctx.qend = kstart_qend(kstart)
-        elif k.shape[1] != q.shape[1] \
-                or _v3_eligible(ext, q, k, causal, klens, dropout_p):
-            # grouped-query K/V exist in the v3 kernels only; the binding
-            # raises on what they do not cover
-            o, lse = ext.flash_attn_fwd_v3(q, k, v, scale, causal, klens,
-                                           dropout_p, seed)
         else:
             o, lse = ext.flash_attn_fwd(q, k, v, scale, causal, klens,
                                         dropout_p, seed)
@@ -218,17 +216,11 @@ class _FlashAttention(torch.autograd.Function):
     def backward(ctx, do):
         q, k, v, o, lse = ctx.saved_tensors
         ext = get_ext()
-        if ctx.kstart is not None:
+        if ctx.v3:
             dq, dk, dv = ext.flash_attn_bwd_v3(
                 q, k, v, o, do.contiguous(), lse, ctx.scale, ctx.causal,
                 ctx.klens, ctx.dropout_p, ctx.seed, kstart=ctx.kstart,
                 qend=ctx.qend)
-        elif k.shape[1] != q.shape[1] \
-                or _v3_eligible(ext, q, k, ctx.causal, ctx.klens,
-                                ctx.dropout_p):
-            dq, dk, dv = ext.flash_attn_bwd_v3(
-                q, k, v, o, do.contiguous(), lse, ctx.scale, ctx.causal,
-                ctx.klens, ctx.dropout_p, ctx.seed)
         else:
             dq, dk, dv = ext.flash_attn_bwd(
                 q, k, v, o, do.contiguous(), lse, ctx.scale, ctx.causal,
@@ -311,14 +303,10 @@ class _PackedFlash(torch.autograd.Function):
         o = torch.empty(b, s, w // (num_heads + 2 * nkv) * num_heads,
                         dtype=qkv.dtype, device=qkv.device)
         ov = o.unflatten(2, (num_heads, -1)).transpose(1, 2)
-        if kstart is not None:
-            lse = get_ext().flash_attn_fwd_v3_strided(
-                q, k, v, ov, scale, causal, klens, kstart=kstart)
-            ctx.qend = kstart_qend(kstart)
-        else:
-            lse = get_ext().flash_attn_fwd_v3_strided(q, k, v, ov, scale,
-                                                      causal, klens)
+        lse = get_ext().flash_attn_fwd_v3_strided(
+            q, k, v, ov, scale, causal, klens, kstart=kstart)
         ctx.kstart = kstart
+        ctx.qend = None if kstart is None else kstart_qend(kstart)
         ctx.save_for_backward(qkv, o, lse)
         ctx.num_heads = num_heads
         ctx.num_kv_heads = nkv
@@ -338,13 +326,11 @@ class _PackedFlash(torch.autograd.Function):
             do = do.contiguous()
         grad = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
         dq, dk, dv = _split_qkv(grad, np_, ctx.num_kv_heads)
-        kw = {}
-        if ctx.kstart is not None:
-            kw = {"kstart": ctx.kstart, "qend": ctx.qend}
         get_ext().flash_attn_bwd_v3_strided(
             q, k, v, o.unflatten(2, (np_, -1)).transpose(1, 2),
             do.unflatten(2, (np_, -1)).transpose(1, 2), lse, dq, dk, dv,
-            ctx.scale, ctx.causal, ctx.klens, **kw)
+            ctx.scale, ctx.causal, ctx.klens, kstart=ctx.kstart,
+            qend=ctx.qend)
         return grad, None, None, None, None, None, None
 
 

@@ -31,12 +31,27 @@ CASES = {
 }
 
 
+# Causal cases with a per-row key start and / or grouped KV heads, each run
+# contiguous and strided.  A table of its own with its own seed base:
+# make_inputs seeds CASES by sorted position, so a new name there would move
+# the inputs of every recorded case.
+# name -> (d, s, h, h_kv, kstart)
+MASKED_CASES = {
+    "d128_causal_s320_kstart": (128, 320, H, H, True),
+    "d64_causal_s128_gqa": (64, 128, 4, 2, False),
+    "d96_causal_s320_gqa_kstart": (96, 320, 4, 1, True),
+}
+
+
 def variants():
     """(case name, strided) pairs, smallest d128 case first."""
     for name, c in CASES.items():
         yield name, False
         if c[6]:
             yield name, True
+    for name in MASKED_CASES:
+        yield name, False
+        yield name, True
 
 
 def key(name, strided):
@@ -44,17 +59,30 @@ def key(name, strided):
 
 
 def make_inputs(name):
-    """q, k, v, dO as [B, H, s, d] bf16 CPU tensors, fixed per case."""
-    d, s = CASES[name][:2]
-    g = torch.Generator(device="cpu").manual_seed(
-        1000 + sorted(CASES).index(name))
-    return [torch.randn(B, H, s, d, generator=g, dtype=torch.float32)
-            .to(torch.bfloat16) for _ in range(4)]
+    """q, k, v, dO as bf16 CPU tensors, fixed per case: q and dO
+    [B, h, s, d], k and v [B, h_kv, s, d] (h = h_kv = H in CASES)."""
+    if name in CASES:
+        (d, s), h, h_kv = CASES[name][:2], H, H
+        seed = 1000 + sorted(CASES).index(name)
+    else:
+        d, s, h, h_kv, _ = MASKED_CASES[name]
+        seed = 2000 + sorted(MASKED_CASES).index(name)
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    return [torch.randn(B, n, s, d, generator=g, dtype=torch.float32)
+            .to(torch.bfloat16) for n in (h, h_kv, h_kv, h)]
 
 
-def _bhsd(x):
-    """[b, s, H*d] -> [b, H, s, d] view."""
-    return x.unflatten(2, (H, -1)).transpose(1, 2)
+def make_kstart(s):
+    """int32 [B, s]: row 0 is packed documents starting at 0, 70 and 200,
+    row 1 is left-padded by 37 (a pad row sees only itself)."""
+    ar = torch.arange(s, dtype=torch.int32)
+    docs = 70 * (ar >= 70) + 130 * (ar >= 200)
+    return torch.stack([docs.to(torch.int32), torch.where(ar < 37, ar, 37)])
+
+
+def _bhsd(x, h=H):
+    """[b, s, h*d] -> [b, h, s, d] view."""
+    return x.unflatten(2, (h, -1)).transpose(1, 2)
 
 
 def _wide(width, s, fill=None):
@@ -66,39 +94,58 @@ def _wide(width, s, fill=None):
 
 
 def run_case(ext, name, strided):
-    """Run forward + backward; returns {o, lse, dq, dk, dv} on the GPU,
-    each [B, H, s, ...] (views for the strided entry)."""
-    d, s, causal, klens, drop_p, drop_seed, _ = CASES[name]
+    """Run forward + backward; returns {o, lse, dq, dk, dv} on the GPU:
+    o, dq [B, h, s, d], dk, dv [B, h_kv, s, d], lse [B, h, s] (views for
+    the strided entry)."""
+    if name in CASES:
+        d, s, causal, klens, drop_p, drop_seed, _ = CASES[name]
+        h, h_kv, masked = H, H, False
+    else:
+        d, s, h, h_kv, masked = MASKED_CASES[name]
+        causal, klens, drop_p, drop_seed = True, None, 0.0, 0
     scale = 1.0 / math.sqrt(d)
     q, k, v, do = [t.cuda() for t in make_inputs(name)]
     kl = None if klens is None else torch.tensor(
         klens, device="cuda", dtype=torch.int32)
+    ks = qe = None
+    if masked:
+        from fengshen_amd.ops.flash import kstart_qend
+        ks = make_kstart(s).cuda()
+        qe = kstart_qend(ks)
     if not strided:
         o, lse = ext.flash_attn_fwd_v3(q, k, v, scale, causal, kl, drop_p,
-                                       drop_seed)
+                                       drop_seed, kstart=ks)
         dq, dk, dv = ext.flash_attn_bwd_v3(q, k, v, o, do, lse, scale,
-                                           causal, kl, drop_p, drop_seed)
+                                           causal, kl, drop_p, drop_seed,
+                                           kstart=ks, qend=qe)
         torch.cuda.synchronize()
         return dict(zip(NAMES, (o, lse, dq, dk, dv)))
 
-    w = H * d
-    _, qkv = _wide(3 * w, s, fill=0.0)
-    qv, kv, vv = [_bhsd(qkv.narrow(2, i * w, w)) for i in range(3)]
+    w, wkv = h * d, h_kv * d
+
+    def parts(x):  # [q | k | v] thirds of a packed [B, s, w + 2*wkv] slice
+        return (_bhsd(x.narrow(2, 0, w), h),
+                _bhsd(x.narrow(2, w, wkv), h_kv),
+                _bhsd(x.narrow(2, w + wkv, wkv), h_kv))
+
+    _, qkv = _wide(w + 2 * wkv, s, fill=0.0)
+    qv, kv, vv = parts(qkv)
     qv.copy_(q), kv.copy_(k), vv.copy_(v)
     _, do_p = _wide(w, s, fill=0.0)
-    _bhsd(do_p).copy_(do)
+    _bhsd(do_p, h).copy_(do)
     o_full, o_p = _wide(w, s)
-    g_full, g_p = _wide(3 * w, s)
-    lse = ext.flash_attn_fwd_v3_strided(qv, kv, vv, _bhsd(o_p), scale,
-                                        causal, kl)
-    dq, dk, dv = [_bhsd(g_p.narrow(2, i * w, w)) for i in range(3)]
-    ext.flash_attn_bwd_v3_strided(qv, kv, vv, _bhsd(o_p), _bhsd(do_p), lse,
-                                  dq, dk, dv, scale, causal, kl)
+    g_full, g_p = _wide(w + 2 * wkv, s)
+    lse = ext.flash_attn_fwd_v3_strided(qv, kv, vv, _bhsd(o_p, h), scale,
+                                        causal, kl, kstart=ks)
+    dq, dk, dv = parts(g_p)
+    ext.flash_attn_bwd_v3_strided(qv, kv, vv, _bhsd(o_p, h), _bhsd(do_p, h),
+                                  lse, dq, dk, dv, scale, causal, kl,
+                                  kstart=ks, qend=qe)
     torch.cuda.synchronize()
-    for full, width in ((o_full, w), (g_full, 3 * w)):  # slice only
+    for full, width in ((o_full, w), (g_full, w + 2 * wkv)):  # slice only
         assert full[:, :, :8].isnan().all(), "wrote in front of the slice"
         assert full[:, :, 8 + width:].isnan().all(), "wrote past the slice"
-    return dict(zip(NAMES, (_bhsd(o_p), lse, dq, dk, dv)))
+    return dict(zip(NAMES, (_bhsd(o_p, h), lse, dq, dk, dv)))
 
 
 def digest(t):

@@ -3,7 +3,9 @@
 tests/golden/flash_v3_parent.json holds SHA-256 digests of O, LSE, dQ, dK
 and dV, written by scripts/gen_flash_v3_golden.py on an MI355X with the
 build before the kernels moved to one LDS image per tile and transposed LDS
-reads.  Inputs come from a CPU generator with a fixed seed.  A change to the
+reads; the kstart and grouped-query entries were added later, from the last
+build with one host launcher per variant, and that build reproduced every
+earlier entry.  Inputs come from a CPU generator with a fixed seed.  A change to the
 kernels that only moves operands (layouts, staging, tile skipping) must
 leave every digest alone; one that reorders a sum will not.  The fp32-oracle
 test at the end keeps a wrong golden file from passing unnoticed.  All tests
@@ -73,3 +75,27 @@ def test_d128_causal_s512_grads_match_fp32_oracle():
     for n, r in (("dq", q.grad), ("dk", k.grad), ("dv", v.grad)):
         err = (res[n].float() - r).abs().max() / r.abs().max().clamp(min=1.0)
         assert err.item() < 3e-2, f"{n}: rel err {err.item():.4g}"
+
+
+def test_strides_of_size_one_dims_are_ignored():
+    """A contiguous tensor may carry any stride on a size-1 dim.  The
+    contiguous entries describe their operands by the sizes, so b = h = 1
+    operands with strides 3 and 5 on those dims give bit for bit what their
+    clones give."""
+    from fengshen_amd.ops import get_ext
+    ext = get_ext()
+    g = torch.Generator(device="cpu").manual_seed(77)
+    odd = [torch.randn(1, 1, 64, 64, generator=g).to(torch.bfloat16).cuda()
+           .as_strided((1, 1, 64, 64), (3, 5, 64, 1)) for _ in range(4)]
+    assert all(t.is_contiguous() and t.stride()[:2] == (3, 5) for t in odd)
+
+    def run(q, k, v, do):
+        o, lse = ext.flash_attn_fwd_v3(q, k, v, 0.125, True, None, 0.0, 0)
+        return (o, lse) + tuple(ext.flash_attn_bwd_v3(
+            q, k, v, o, do, lse, 0.125, True, None, 0.0, 0))
+
+    got = run(*odd)
+    want = run(*[t.clone(memory_format=torch.contiguous_format)
+                 for t in odd])
+    for n, x, y in zip(gen.NAMES, got, want):
+        assert not x.float().isnan().any() and torch.equal(x, y), n

@@ -2,6 +2,7 @@
 batches: the mask conversions, the dkv loop bound, the collator padding and
 the model wiring, all on the CPU.  The kernels themselves are checked in
 test_flash_varlen_gpu.py."""
+import pytest
 import torch
 
 from fengshen_amd.ops.flash import (
@@ -214,3 +215,56 @@ def test_gpt2_kstart_equals_reset_attention_mask_on_cpu():
         plain = model(tok, position_ids=pos).logits
     assert torch.equal(got, want)
     assert not torch.equal(plain[0], got[0])
+
+
+class _StubExt:
+    """Stands in for the HIP extension (no GPU): records the entries that
+    _FlashAttention calls and returns tensors of the right shapes."""
+
+    def __init__(self):
+        self.calls = []
+
+    def _fwd(self, name, q):
+        self.calls.append(name)
+        return torch.zeros_like(q), torch.zeros(q.shape[:3])
+
+    def _bwd(self, name, q, k, v):
+        self.calls.append(name)
+        return torch.zeros_like(q), torch.zeros_like(k), torch.zeros_like(v)
+
+    def flash_attn_fwd_v3(self, q, k, v, *args, **kw):
+        return self._fwd("fwd_v3", q)
+
+    def flash_attn_fwd(self, q, k, v, *args):
+        return self._fwd("fwd_v1", q)
+
+    def flash_attn_bwd_v3(self, q, k, v, *args, **kw):
+        return self._bwd("bwd_v3", q, k, v)
+
+    def flash_attn_bwd(self, q, k, v, *args):
+        return self._bwd("bwd_v1", q, k, v)
+
+
+@pytest.mark.parametrize("set_in_forward", [True, False])
+def test_flash_route_is_decided_once_in_forward(monkeypatch, set_in_forward):
+    """Dropout at d = 64 goes to v3 only under FENGSHEN_FLASH_V3_DROP=1.
+    Backward must follow the kernel family that forward used (it reads that
+    family's lse), whatever the variable says by then."""
+    from fengshen_amd.ops import flash
+    stub = _StubExt()
+    monkeypatch.setattr(flash, "get_ext", lambda: stub)
+    var = "FENGSHEN_FLASH_V3_DROP"
+    if set_in_forward:
+        monkeypatch.setenv(var, "1")
+    else:
+        monkeypatch.delenv(var, raising=False)
+    q, k, v = [torch.zeros(1, 2, 64, 64, dtype=torch.bfloat16,
+                           requires_grad=True) for _ in range(3)]
+    o = flash._FlashAttention.apply(q, k, v, 0.125, True, None, 0.1, 7)
+    if set_in_forward:
+        monkeypatch.delenv(var)
+    else:
+        monkeypatch.setenv(var, "1")
+    o.sum().backward()
+    family = "v3" if set_in_forward else "v1"
+    assert stub.calls == ["fwd_" + family, "bwd_" + family]

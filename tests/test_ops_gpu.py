@@ -480,6 +480,48 @@ def test_flash_bwd_v3_matches_oracle(s):
     _close(v.grad, v2.grad, 3e-2)
 
 
+def test_flash_v3_contiguous_entries_refuse_bad_operands():
+    """The plain path (no kstart, h_kv == h) of the contiguous v3 entries
+    raises on operands the kernels cannot take, before anything is
+    launched."""
+    from fengshen_amd.ops import get_ext
+    ext = get_ext()
+    b, h, s, d = 2, 2, 64, 64
+    q, k, v, do = [_rand(b, h, s, d, seed=i) for i in range(4)]
+    klens = torch.full((b,), s, dtype=torch.int32, device="cuda")
+    o, lse = ext.flash_attn_fwd_v3(q, k, v, 0.125, False, klens, 0.0, 0)
+
+    def fwd(q=q, k=k, v=v, klens=klens):
+        return ext.flash_attn_fwd_v3(q, k, v, 0.125, False, klens, 0.0, 0)
+
+    def bwd(q=q, k=k, v=v, klens=klens, o=o, lse=lse, qend=None):
+        return ext.flash_attn_bwd_v3(q, k, v, o, do, lse, 0.125, False, klens,
+                                     0.0, 0, qend=qend)
+
+    both = [
+        dict(v=_rand(b, h, 2 * s, d)),                     # another s
+        dict(k=k.half()),
+        dict(q=_rand(b, s, h, d).transpose(1, 2)),         # not contiguous
+        dict(klens=klens.cpu()),
+        dict(klens=klens.long()),
+        dict(klens=torch.full((b + 1,), s, dtype=torch.int32,
+                              device="cuda")),
+    ]
+    bwd_only = [
+        dict(lse=lse.flatten()[:-1]),
+        dict(o=_rand(b, h, s, 2 * d)),
+        dict(qend=torch.zeros(b, s // 64, dtype=torch.int32, device="cuda")),
+    ]
+    for fn, cases in ((fwd, both), (bwd, both + bwd_only)):
+        for kw in cases:
+            with pytest.raises(RuntimeError):
+                fn(**kw)
+    torch.cuda.synchronize()
+    # the same calls with good operands go through
+    assert torch.equal(fwd()[0], o)
+    assert all(t.isfinite().all() for t in bwd())
+
+
 def test_fused_vocab_ce_matches_composite():
     """Fused CE (per-row stats, bwd recompute) vs the composite
     vocab-parallel CE and torch.nn CE, incl. ignored (-100) rows."""
