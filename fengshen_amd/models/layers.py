@@ -257,11 +257,7 @@ class ParallelAttention(nn.Module):
             k, v = expand_kv(k, np_), expand_kv(v, np_)
         ctx = self.sparse_attn(q.contiguous(), k.contiguous(), v.contiguous(),
                                attention_mask=keep, scale=self.norm_factor)
-        ctx = ctx.transpose(1, 2).reshape(b, sq, np_ * hn)
-        out = self.out_proj(ctx)
-        if isinstance(out, tuple) and self.reduce_output:
-            out = out[0]
-        return out
+        return self._project_out(ctx.transpose(1, 2).reshape(b, sq, np_ * hn))
 
     def _split_heads(self, qkv):
         """[b, s, (np + 2*nkv)*hn] -> q [b, np, s, hn], k/v [b, nkv, s, hn]
@@ -303,35 +299,30 @@ class ParallelAttention(nn.Module):
         if self.sparse_attn is not None:
             return self._sparse_forward(qkv, attention_mask, cache)
 
-        # packed path: rotary in place + strided flash kernels on the
-        # projection output itself — no chunk/transpose/contiguous copies
-        if cache is None and F_ops.use_hip(qkv):
-            from fengshen_amd.ops.flash import (
-                mask_to_klens, mask_to_kstart, packed_attn_eligible,
-                packed_self_attention, varlen_flash_enabled)
-            drop = self.attention_dropout if self.training else 0.0
-            masked = attention_mask is not None or kstart is not None
-            if packed_attn_eligible(qkv, hn, self.causal,
-                                    attention_mask if kstart is None
-                                    else kstart, drop, np_, nkv):
-                klens = ks = None
-                if self.causal and masked and varlen_flash_enabled():
-                    ks = kstart if kstart is not None else \
-                        mask_to_kstart(attention_mask, sq)
-                elif not self.causal and attention_mask is not None:
-                    klens = mask_to_klens(attention_mask, sq)
-                if not masked or klens is not None or ks is not None:
-                    cos = sin = None
-                    if self.rotary:
-                        cos, sin = self._rope_tables(qkv.device, sq)
-                    ctx = packed_self_attention(
-                        qkv, np_, cos, sin, 0, self.norm_factor,
-                        causal=self.causal, klens=klens, kstart=ks,
-                        num_kv_heads=nkv)
-                    out = self.out_proj(ctx)
-                    if isinstance(out, tuple) and self.reduce_output:
-                        out = out[0]
-                    return out
+        # one routing decision (ops.flash.route_attention).  Without a
+        # cache it is taken here, on the projection output: the packed path
+        # is rotary in place + strided flash kernels on that buffer, no
+        # chunk/transpose/contiguous copies; otherwise the decision (and
+        # the mask conversion in it) goes along to F_ops.attention.
+        route = None
+        if cache is None:
+            from fengshen_amd.ops import flash
+            on_gpu = F_ops.use_hip(qkv)
+            route = flash.route_attention(
+                on_gpu=on_gpu, dtype=qkv.dtype, heads=np_, kv_heads=nkv,
+                sq=sq, sk=sq, head_dim=hn, causal=self.causal,
+                mask=attention_mask, kstart=kstart,
+                dropout_p=self.attention_dropout if self.training else 0.0,
+                packed_ok=on_gpu and flash.packed_layout_ok(qkv))
+            if route.path == "packed":
+                cos = sin = None
+                if self.rotary:
+                    cos, sin = self._rope_tables(qkv.device, sq)
+                # looked up at call time: tests replace it on the module
+                return self._project_out(flash.packed_self_attention(
+                    qkv, np_, cos, sin, 0, self.norm_factor,
+                    causal=self.causal, klens=route.klens,
+                    kstart=route.kstart, num_kv_heads=nkv))
 
         # [b, s, n, hn] -> [b, n, s, hn]
         q, k, v = self._split_heads(qkv)
@@ -356,8 +347,10 @@ class ParallelAttention(nn.Module):
         ctx = F_ops.attention(q, k, v, causal=causal, mask=attention_mask,
                               dropout_p=self.attention_dropout,
                               training=self.training, scale=self.norm_factor,
-                              kstart=kstart)
-        ctx = ctx.transpose(1, 2).reshape(b, sq, np_ * hn)
+                              kstart=kstart, route=route)
+        return self._project_out(ctx.transpose(1, 2).reshape(b, sq, np_ * hn))
+
+    def _project_out(self, ctx):
         out = self.out_proj(ctx)
         if isinstance(out, tuple) and self.reduce_output:
             out = out[0]

@@ -17,53 +17,47 @@ generality (ref flash_attention.py:174 call semantics):
   j uses KV head j // (h / h_kv) (HF ``repeat_kv`` order).  Native in the
   causal v3 kernels without dropout, with or without ``kstart``; K/V are
   never expanded and dK/dV come back with h_kv heads.
+
+Which of these a call gets is decided in one place, ``route_attention``
+(table: docs/KERNELS.md, "Attention routing").
 """
 from __future__ import annotations
 
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
 from fengshen_amd.ops import get_ext
 
 _FLASH_DIMS = (40, 64, 80, 96, 128, 160)
+_V3_DIMS = (64, 96, 128)
 
 
-def _v3_eligible(ext, q, k, causal, klens, dropout_p):
-    """v3 (swapped-QK^T 32x32 schedule, ~1.8x): self-attention at
-    d in {64, 96, 128} with s % 64 == 0; causal or klens-masked bidirectional.
-    Dropout routes to the general kernels by default: a same-box A/B on
+def _v3_seq(sq: int, sk: int) -> bool:
+    return sq == sk and sq % 64 == 0 and sq >= 64
+
+
+def _v3_shape(head_dim: int, sq: int, sk: int) -> bool:
+    """Shapes of the v3 kernels (swapped-QK^T 32x32 schedule, ~1.8x):
+    self-attention over a whole number of 64-row tiles."""
+    return head_dim in _V3_DIMS and _v3_seq(sq, sk)
+
+
+def _v3_dropout(head_dim: int) -> bool:
+    """Dropout runs on the general kernels by default: a same-box A/B on
     the BERT step (b128 s512 d64 p=0.1) measured them identical (177.2
-    vs 177.5/178.8 samples/s — the step is no longer attention-bound),
+    vs 177.5/178.8 samples/s -- the step is no longer attention-bound),
     so the simpler routing stands; FENGSHEN_FLASH_V3_DROP=1 flips
     dropout onto v3 at d 64/96 for experiments."""
-    if not (hasattr(ext, "flash_attn_fwd_v3")
-            and q.shape[-1] in (64, 96, 128)
-            and q.shape[-2] == k.shape[-2]
-            and q.shape[-2] % 64 == 0 and q.shape[-2] >= 64):
-        return False
-    if dropout_p > 0:
-        return os.environ.get("FENGSHEN_FLASH_V3_DROP") == "1" \
-            and q.shape[-1] in (64, 96)
-    return True
+    return os.environ.get("FENGSHEN_FLASH_V3_DROP") == "1" \
+        and head_dim in (64, 96)
 
 
 def gqa_flash_enabled() -> bool:
     """FENGSHEN_GQA_FLASH=0 expands K/V to the query heads in front of
     every attention path instead of using the grouped-query kernels."""
     return os.environ.get("FENGSHEN_GQA_FLASH", "1") != "0"
-
-
-def gqa_flash_supported(q: torch.Tensor, k: torch.Tensor, causal: bool,
-                        dropout_p: float) -> bool:
-    """Calls the grouped-query kernels cover: bf16 on the GPU, causal
-    self-attention at v3 shapes, no dropout (a mask must reduce to kstart —
-    the caller's check)."""
-    return (gqa_flash_enabled() and causal and q.is_cuda
-            and q.shape[1] % k.shape[1] == 0
-            and kstart_supported(q.shape[-1], q.shape[-2], k.shape[-2],
-                                 q.dtype, dropout_p))
 
 
 def expand_kv(x: torch.Tensor, num_heads: int) -> torch.Tensor:
@@ -83,13 +77,6 @@ def varlen_flash_enabled() -> bool:
     """FENGSHEN_VARLEN_FLASH=0 keeps causal attention under a mask on the
     bmm + masked-softmax path."""
     return os.environ.get("FENGSHEN_VARLEN_FLASH", "1") != "0"
-
-
-def kstart_supported(head_dim: int, sq: int, sk: int, dtype,
-                     dropout_p: float) -> bool:
-    """Shapes the kstart kernels cover."""
-    return (dtype == torch.bfloat16 and head_dim in (64, 96, 128)
-            and sq == sk and sq % 64 == 0 and sq >= 64 and dropout_p == 0)
 
 
 def kstart_qend(kstart: torch.Tensor) -> torch.Tensor:
@@ -179,8 +166,8 @@ def model_kstart(mask: Optional[torch.Tensor], x: torch.Tensor
     if mask is None or not varlen_flash_enabled():
         return None
     s = x.shape[1]
-    if not (x.is_cuda and x.dtype == torch.bfloat16 and s % 64 == 0
-            and s >= 64 and mask.shape[-1] == s):
+    if not (x.is_cuda and x.dtype == torch.bfloat16
+            and _v3_seq(s, mask.shape[-1])):
         return None
     return mask_to_kstart(mask, s)
 
@@ -194,8 +181,10 @@ class _FlashAttention(torch.autograd.Function):
         # must read the lse of the family that wrote it.  kstart and
         # grouped-query K/V exist in the v3 kernels only -- no quiet
         # fall-back, the binding raises on what they do not cover.
+        d = q.shape[-1]
         ctx.v3 = (kstart is not None or k.shape[1] != q.shape[1]
-                  or _v3_eligible(ext, q, k, causal, klens, dropout_p))
+                  or (_v3_shape(d, q.shape[-2], k.shape[-2])
+                      and (dropout_p == 0 or _v3_dropout(d))))
         ctx.kstart = kstart
         ctx.qend = None if kstart is None else kstart_qend(kstart)
         if ctx.v3:
@@ -334,29 +323,10 @@ class _PackedFlash(torch.autograd.Function):
         return grad, None, None, None, None, None, None
 
 
-def packed_attn_eligible(qkv, head_dim: int, causal: bool, mask,
-                         dropout_p: float, num_heads: Optional[int] = None,
-                         num_kv_heads: Optional[int] = None) -> bool:
-    """True when self-attention can run on the packed [b, s, (np+2*nkv)*hn]
-    projection output in place: v3 shapes (d in {64, 96, 128}, s % 64 == 0),
-    bf16, no dropout.  Grouped-query layouts (num_kv_heads != num_heads)
-    are causal only and off under FENGSHEN_GQA_FLASH=0.  A mask must still reduce to klens (bidirectional)
-    or to kstart (causal) — checked by the caller; under causal a mask is
-    refused outright when FENGSHEN_VARLEN_FLASH=0.  FENGSHEN_PACKED_ATTN=0
-    forces the chunk/transpose/contiguous path."""
-    if os.environ.get("FENGSHEN_PACKED_ATTN", "1") == "0":
-        return False
-    if qkv.dtype != torch.bfloat16 or qkv.dim() != 3 or dropout_p > 0:
-        return False
-    if num_kv_heads is not None and num_kv_heads != num_heads \
-            and not (causal and gqa_flash_enabled()):
-        return False
-    s = qkv.shape[1]
-    if head_dim not in (64, 96, 128) or s % 64 != 0 or s < 64:
-        return False
-    if causal and mask is not None and not varlen_flash_enabled():
-        return False
-    return (qkv.stride(2) == 1 and qkv.stride(0) % 8 == 0
+def packed_layout_ok(qkv: torch.Tensor) -> bool:
+    """The layout the strided kernels read in place: [b, s, w] with a
+    unit-stride last dim and everything else a multiple of 8 elements."""
+    return (qkv.dim() == 3 and qkv.stride(2) == 1 and qkv.stride(0) % 8 == 0
             and qkv.stride(1) % 8 == 0 and qkv.storage_offset() % 8 == 0)
 
 
@@ -433,14 +403,59 @@ def mask_to_klens(mask: torch.Tensor, sk: int) -> Optional[torch.Tensor]:
     return klens.contiguous()
 
 
-def flash_attn_supported(q, k, v, causal, mask, dropout_p) -> bool:
-    if q.dtype != torch.bfloat16:
-        return False
-    if q.shape[-1] not in _FLASH_DIMS:
-        return False
-    sq, sk = q.shape[-2], k.shape[-2]
+class AttnRoute(NamedTuple):
+    """What route_attention decided.  path: "packed" (strided v3 kernels on
+    the QKV buffer, packed_self_attention), "flash" (flash_attention) or
+    "bmm" (scores, softmax, PV)."""
+    path: str
+    klens: Optional[torch.Tensor] = None   # for the kernels, non-causal
+    kstart: Optional[torch.Tensor] = None  # for the kernels, causal
+    expand_kv: bool = False   # grouped K/V go to the query heads first
+    mask: Optional[torch.Tensor] = None    # bmm only: the dense mask
+
+
+def route_attention(*, on_gpu: bool, dtype, heads: int, kv_heads: int,
+                    sq: int, sk: int, head_dim: int, causal: bool,
+                    mask: Optional[torch.Tensor] = None,
+                    kstart: Optional[torch.Tensor] = None,
+                    dropout_p: float = 0.0,
+                    packed_ok: bool = False) -> AttnRoute:
+    """The one place that decides which kernels an attention call runs
+    (table: docs/KERNELS.md, "Attention routing").  Host logic only: on_gpu
+    is what use_hip said, dropout_p is 0 outside training, packed_ok says
+    that the caller holds a packed QKV buffer of a layout the strided
+    kernels read (packed_layout_ok) and no KV cache.  mask (True = masked)
+    is converted at most once, with one device-to-host sync; a given kstart
+    wins over it and the mask is then not inspected."""
+    if kstart is not None and not (causal and sq == sk):
+        raise ValueError("kstart needs causal self-attention (sq == sk)")
+    kernels = on_gpu and dtype == torch.bfloat16
+    v3 = kernels and _v3_shape(head_dim, sq, sk) and dropout_p == 0
+    grouped = kv_heads != heads
+    # the grouped-query kernels are causal v3 without dropout; every other
+    # call expands K/V and goes on as for kv_heads == heads
+    native = grouped and causal and v3 and heads % kv_heads == 0 \
+        and gqa_flash_enabled()
+    packed = packed_ok and v3 and (native or not grouped) \
+        and os.environ.get("FENGSHEN_PACKED_ATTN", "1") != "0"
+    klens = ks = None
     if causal:
-        return mask is None and sq == sk and sq % 64 == 0
-    # bidirectional: sq tiles at 16; sk arbitrary; mask must convert to
-    # suffix-pad klens (checked by the caller via mask_to_klens)
-    return sq % 16 == 0 and sq >= 16
+        masked = mask is not None or kstart is not None
+        if masked and v3 and varlen_flash_enabled():
+            ks = kstart if kstart is not None else mask_to_kstart(mask, sq)
+        # unmasked, the general kernels take any s % 64 == 0, and dropout
+        run = ks is not None or (
+            not masked and kernels and head_dim in _FLASH_DIMS
+            and sq == sk and sq % 64 == 0)
+    else:
+        run = kernels and head_dim in _FLASH_DIMS and sq % 16 == 0 \
+            and sq >= 16
+        if run and mask is not None:
+            klens = mask_to_klens(mask, sk)
+            run = klens is not None
+    if run:
+        return AttnRoute("packed" if packed else "flash", klens, ks,
+                         grouped and not native)
+    if mask is None and kstart is not None:
+        mask = kstart_to_mask(kstart)
+    return AttnRoute("bmm", expand_kv=grouped, mask=mask)

@@ -554,19 +554,20 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
               causal: bool = False, mask: Optional[torch.Tensor] = None,
               dropout_p: float = 0.0, training: bool = False,
               scale: Optional[float] = None,
-              kstart: Optional[torch.Tensor] = None) -> torch.Tensor:
+              kstart: Optional[torch.Tensor] = None,
+              route=None) -> torch.Tensor:
     """q: [b, np, sq, hn], k,v: [b, nkv, sk, hn] -> context [b, np, sq, hn].
 
     nkv < np is grouped-query attention (np % nkv == 0, query head j uses
-    KV head j // (np / nkv)).  The grouped-query flash kernels take it when
-    they cover the call (GPU, bf16, causal with sq == sk, hn in {64, 96,
-    128}, s % 64 == 0, no active dropout, mask absent or reducible to
-    kstart); everything else, and everything under FENGSHEN_GQA_FLASH=0,
-    expands K/V to np heads and proceeds as for nkv == np, autograd summing
-    the group's gradients.
+    KV head j // (np / nkv)); where the grouped-query kernels do not cover
+    the call, K/V are expanded to np heads and autograd sums the group's
+    gradients.
 
-    GPU path: flash-style fused HIP kernel when available (csrc/flash_attn.hip)
-    else hipBLASLt bmm + fused-softmax kernel.  CPU path: eager oracle.
+    Which kernels run -- flash, or hipBLASLt bmm + the fused softmax; on the
+    CPU the eager oracle -- is decided by ops.flash.route_attention alone
+    (table: docs/KERNELS.md, "Attention routing").  ``route`` is for a
+    caller that has already asked it for exactly this call: the decision is
+    then taken as given and the mask is not looked at again.
 
     kstart (int32 [b, s], causal self-attention only): row i sees keys
     kstart[i] <= j <= i (ops/flash.py).  Callers that have it pass it
@@ -574,58 +575,25 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     given without it is converted when it is of that form.  Shapes the
     kstart kernels do not cover run under the dense mask as before.
     """
+    from fengshen_amd.ops.flash import (
+        expand_kv, flash_attention, route_attention)
     b, np_, sq, hn = q.shape
     sk = k.shape[-2]
     if scale is None:
         scale = 1.0 / math.sqrt(hn)
-    if kstart is not None and not (causal and sq == sk):
-        raise ValueError("kstart needs causal self-attention (sq == sk)")
-    ext = get_ext() if use_hip(q) else None
-    if k.shape[1] != np_:
-        from fengshen_amd.ops.flash import (
-            expand_kv, flash_attention, gqa_flash_supported, mask_to_kstart,
-            varlen_flash_enabled)
-        drop = dropout_p if training else 0.0
-        if ext is not None and hasattr(ext, "flash_attn_fwd_v3") \
-                and gqa_flash_supported(q, k, causal, drop):
-            ks = kstart
-            if (ks is not None or mask is not None) \
-                    and not varlen_flash_enabled():
-                ks = None
-            elif ks is None and mask is not None:
-                ks = mask_to_kstart(mask, sq)
-            if ks is not None or (mask is None and kstart is None):
-                return flash_attention(q, k, v, scale, causal=True, kstart=ks)
+    drop = dropout_p if training else 0.0
+    if route is None:
+        route = route_attention(
+            on_gpu=use_hip(q), dtype=q.dtype, heads=np_, kv_heads=k.shape[1],
+            sq=sq, sk=sk, head_dim=hn, causal=causal, mask=mask,
+            kstart=kstart, dropout_p=drop)
+    if route.expand_kv:
         k, v = expand_kv(k, np_), expand_kv(v, np_)
-    if ext is not None and hasattr(ext, "flash_attn_fwd"):
-        from fengshen_amd.ops.flash import (
-            flash_attention, flash_attn_supported, kstart_supported,
-            mask_to_klens, mask_to_kstart, varlen_flash_enabled)
-        drop = dropout_p if training else 0.0
-        if causal and (mask is not None or kstart is not None) \
-                and varlen_flash_enabled() \
-                and kstart_supported(hn, sq, sk, q.dtype, drop):
-            ks = kstart if kstart is not None else mask_to_kstart(mask, sq)
-            if ks is not None:
-                return flash_attention(q, k, v, scale, causal=True,
-                                       kstart=ks)
-        if mask is None and kstart is not None:
-            from fengshen_amd.ops.flash import kstart_to_mask
-            mask = kstart_to_mask(kstart)
-        if flash_attn_supported(q, k, v, causal, mask, drop):
-            if causal and mask is None:
-                return flash_attention(q, k, v, scale, causal=True,
-                                       dropout_p=drop)
-            if not causal:
-                klens = None
-                if mask is not None:
-                    klens = mask_to_klens(mask, sk)
-                if mask is None or klens is not None:
-                    return flash_attention(q, k, v, scale, causal=False,
-                                           klens=klens, dropout_p=drop)
-    if mask is None and kstart is not None:
-        from fengshen_amd.ops.flash import kstart_to_mask
-        mask = kstart_to_mask(kstart)
+    if route.path == "flash":
+        return flash_attention(q, k, v, scale, causal=causal,
+                               klens=route.klens, dropout_p=drop,
+                               kstart=route.kstart)
+    mask = route.mask
     # bmm path: scores in [b*np, sq, sk]
     q2 = q.reshape(b * np_, sq, hn)
     k2 = k.reshape(b * np_, sk, hn)
