@@ -72,6 +72,8 @@ void fs_decode_attn(const void*, void*, void*, const float*, const float*,
                     hipStream_t);
 void fs_w8_gemv(const void*, const float*, const void*, void*, int, int, int,
                 hipStream_t);
+void fs_decode_gemm(const void*, const float*, const void*, void*, int, int,
+                    int, int, hipStream_t);
 void fs_vocab_ce_fwd(const void*, const long*, float*, float*, float*,
                      long, int, int, int, hipStream_t);
 void fs_vocab_ce_bwd(const void*, const long*, const float*, const float*,
@@ -857,6 +859,46 @@ static at::Tensor bf16_gemv(at::Tensor w, at::Tensor x) {
   return y;
 }
 
+// Weight-streaming MFMA GEMM for 1..16 rows (decode_gemm.hip):
+// w [out, K] bf16, or int8 with scale [out] fp32; x [..., K] bf16 with 1..16
+// rows -> y [rows, out] bf16.  Allocates nothing but y.
+static at::Tensor decode_gemm(at::Tensor w, at::Tensor x,
+                              c10::optional<at::Tensor> scale) {
+  const bool w8 = w.scalar_type() == at::kChar;
+  TORCH_CHECK(w.dim() == 2 && w.is_contiguous() &&
+                  (w8 || w.scalar_type() == at::kBFloat16),
+              "decode_gemm: w must be contiguous 2-D bf16 or int8");
+  const int64_t out = w.size(0), K = w.size(1);
+  TORCH_CHECK(out >= 1 && out < (1LL << 31) && K >= 64 && K < (1LL << 31) &&
+                  K % 64 == 0,
+              "decode_gemm: w must be [out >= 1, K] with K a positive "
+              "multiple of 64, got [", out, ", ", K, "]");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_contiguous() &&
+                  x.dim() >= 1 && x.size(-1) == K,
+              "decode_gemm: x must be contiguous bf16 [..., ", K, "]");
+  const int64_t rows = x.numel() / K;
+  TORCH_CHECK(rows >= 1 && rows <= 16,
+              "decode_gemm: x must have 1..16 rows, got ", rows);
+  TORCH_CHECK(scale.has_value() == w8,
+              "decode_gemm: scale must be given exactly when w is int8");
+  if (w8)
+    TORCH_CHECK(scale->scalar_type() == at::kFloat && scale->is_contiguous() &&
+                    scale->dim() == 1 && scale->size(0) == out &&
+                    scale->is_cuda() && scale->device() == w.device(),
+                "decode_gemm: scale must be contiguous fp32 [", out,
+                "] on w's device");
+  TORCH_CHECK(w.is_cuda() && x.is_cuda() && x.device() == w.device(),
+              "decode_gemm: w and x must be on the same GPU");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(w.data_ptr()) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15) == 0,
+              "decode_gemm: w and x must be 16-byte aligned");
+  auto y = at::empty({rows, out}, x.options());
+  fs_decode_gemm(w.data_ptr(), w8 ? scale->data_ptr<float>() : nullptr,
+                 x.data_ptr(), y.data_ptr(), (int)rows, (int)K, (int)out,
+                 w8 ? 1 : 0, cur_stream());
+  return y;
+}
+
 // Fused decode step: qkv [b, (nh + 2*nkv)*d] bf16, kc/vc [b, nkv, L, d] bf16
 // caches (written in-place at pos), cos/sin [max_len, d] fp32, pos [1] long.
 // nkv comes from the caches and nh from the width of qkv (nkv == nh: plain
@@ -1115,6 +1157,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("w8_gemv", &w8_gemv);
   mod.def("bf16_gemv", &bf16_gemv);
   mod.def("decode_attn", &decode_attn);
+  mod.def("decode_gemm", &decode_gemm, py::arg("w"), py::arg("x"),
+          py::arg("scale") = py::none());
   mod.def("decode_attn_split", &decode_attn_split, py::arg("qkv"),
           py::arg("kc"), py::arg("vc"), py::arg("cos"), py::arg("sin"),
           py::arg("pos"), py::arg("scale"), py::arg("rope"),

@@ -465,24 +465,78 @@ def swiglu_mlp_residual(h2, residual, w_gate_up, w_down,
                                     output_unused)
 
 
+# FENGSHEN_DECODE_GEMM=auto: from this many rows up to 16, a bias-free bf16
+# decode linear runs decode_gemm (decode_gemm.hip) instead of hipBLASLt
+# (bf16 weights) or w8_gemv (int8 weights); None = never under auto.  Set
+# from scripts/decode_gemm_bench.py to the smallest measured row count from
+# which decode_gemm wins at all five 13B shapes (docs/KERNELS.md,
+# "decode_gemm.hip"), and never below 3: one-row calls and the two-row calls
+# of the earlier decode tests keep the kernels they always ran.
+# Measured: int8 wins at every shape from 4 rows (2-6x at 8 and 16; at 2 rows
+# it loses at 5120 x 5120); bf16 loses to hipBLASLt at 8 and 16 rows at four
+# of the five shapes, so auto never routes bf16 weights to it.
+_DECODE_GEMM_MIN_ROWS = {torch.bfloat16: None, torch.int8: 4}
+
+
+def decode_gemm_mode() -> str:
+    mode = os.environ.get("FENGSHEN_DECODE_GEMM", "auto")
+    if mode not in ("auto", "0", "1"):
+        raise ValueError("FENGSHEN_DECODE_GEMM must be auto, 0 or 1, "
+                         f"got {mode!r}")
+    return mode
+
+
+def decode_linear_route(rows: int, in_features: int, weight_dtype,
+                        on_gpu: bool, grad_enabled: bool, mode: str) -> str:
+    """Which kernel a bias-free linear on bf16 activations runs:
+
+    "gemv"         bf16_gemv (bf16 weights, one row) or w8_gemv (int8
+                   weights, up to 16 rows): what ran before decode_gemm
+    "decode_gemm"  the MFMA weight-streaming kernel, 2..16 rows, K % 64 == 0
+    "library"      F.linear, or the dequantised matmul for int8 weights
+
+    on_gpu means the HIP path is usable for the call (use_hip) and the
+    activations are bf16.  mode is FENGSHEN_DECODE_GEMM: "0" never picks
+    decode_gemm, "1" picks it wherever it can run, "auto" from
+    _DECODE_GEMM_MIN_ROWS[weight_dtype] rows.  This is the only place that
+    decides."""
+    w8 = weight_dtype == torch.int8
+    if not on_gpu or not (w8 or weight_dtype == torch.bfloat16):
+        return "library"
+    if not w8 and grad_enabled:
+        return "library"
+    if in_features % 16 != 0:
+        return "library"
+    if 2 <= rows <= 16 and in_features % 64 == 0 and not grad_enabled:
+        min_rows = _DECODE_GEMM_MIN_ROWS[weight_dtype]
+        if mode == "1" or (mode == "auto" and min_rows is not None
+                           and rows >= min_rows):
+            return "decode_gemm"
+    if (rows <= 16) if w8 else (rows == 1):
+        return "gemv"
+    return "library"
+
+
 def linear(x: torch.Tensor, weight: torch.Tensor,
            bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """F.linear with a decode fast path: for inference-shaped inputs
-    (<=8 rows, bf16, no bias) the hand-written bf16 GEMV kernel streams
-    the weight matrix at HBM rate instead of hipBLASLt's skinny-M GEMM
-    tiles.  Falls back to F.linear everywhere else (training, CPU,
-    other dtypes) so autograd semantics are unchanged."""
-    if (bias is None and x.is_cuda and x.dtype == torch.bfloat16
-            and weight.dtype == torch.bfloat16
-            and not torch.is_grad_enabled()
-            and weight.shape[1] % 16 == 0
-            and x.shape[-1] == weight.shape[1]):
+    """F.linear with two decode fast paths for bias-free bf16 inference
+    calls, chosen by decode_linear_route: one row runs the bf16 GEMV
+    kernel, 2..16 rows can run decode_gemm, the MFMA weight-streaming
+    kernel (FENGSHEN_DECODE_GEMM = auto | 0 | 1); both stream the weight
+    matrix once instead of going through hipBLASLt's skinny-M GEMM tiles.
+    F.linear everywhere else (training, CPU, other dtypes, a bias), so
+    autograd semantics are unchanged."""
+    if bias is None and x.shape[-1] == weight.shape[1]:
         rows = x.numel() // x.shape[-1]
-        # rows == 1 only: the B>1 GEMV re-reads x per weight vector and
-        # measured SLOWER than hipBLASLt's M=8 GEMM (17.2 vs 11.0 ms/tok
-        # at batch 8) — multi-row decode stays on the library path.
-        if rows == 1 and use_hip(x):
+        route = decode_linear_route(
+            rows, weight.shape[1], weight.dtype,
+            use_hip(x) and x.dtype == torch.bfloat16,
+            torch.is_grad_enabled(), decode_gemm_mode())
+        if route == "gemv":
             y = get_ext().bf16_gemv(weight.contiguous(), x.contiguous())
+            return y.view(*x.shape[:-1], weight.shape[0])
+        if route == "decode_gemm":
+            y = get_ext().decode_gemm(weight.contiguous(), x.contiguous())
             return y.view(*x.shape[:-1], weight.shape[0])
     return torch.nn.functional.linear(x, weight, bias)
 

@@ -20,6 +20,13 @@ hipGraph on ROCm) and replays it per token:
   dim 96 and ragged prompt batches (generate(..., prompt_lens=...)), which
   decode_attn cannot, and long windows; FENGSHEN_DECODE_SPLIT = auto | 0 | 1
   picks between the two (see _SPLIT_MIN_LEN);
+- with a batch of 2..16 the projections and the LM head can run decode_gemm
+  (decode_gemm.hip), an MFMA kernel that streams the weights once and gets
+  the reuse of x across the batch from the matrix instruction;
+  FENGSHEN_DECODE_GEMM = auto | 0 | 1, read per call by
+  ops.functional.decode_linear_route.  auto takes it for int8 weights
+  (W8Linear) from 4 rows, where it replaces w8_gemv, whose cost grows with
+  the batch; bf16 weights keep hipBLASLt, which measured faster;
 - greedy argmax — or gumbel-max top-k/top-p sampling over a pre-generated
   seeded noise buffer indexed by the step tensor — feeds the token buffer
   consumed by the NEXT replay, so a whole max_new_tokens decode is just N

@@ -13,7 +13,12 @@ import torch.nn as nn
 
 
 class W8Linear(nn.Module):
-    """int8 weight + per-output-channel fp scale; bf16 activations."""
+    """int8 weight + per-output-channel fp scale; bf16 activations.
+
+    Up to 16 rows of bf16 activations on the GPU stay in int8 in HBM:
+    ops.functional.decode_linear_route picks w8_gemv or, for 2..16 rows,
+    decode_gemm (FENGSHEN_DECODE_GEMM = auto | 0 | 1).  Everything else
+    dequantises the weight and calls F.linear."""
 
     def __init__(self, weight: torch.Tensor, bias=None):
         super().__init__()
@@ -31,12 +36,21 @@ class W8Linear(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         from fengshen_amd.ops import use_hip, get_ext
+        from fengshen_amd.ops.functional import (
+            decode_gemm_mode, decode_linear_route)
         rows = x.numel() // x.shape[-1]
-        if (use_hip(x) and x.dtype == torch.bfloat16 and rows <= 16
-                and x.shape[-1] % 16 == 0):
-            # decode path: fused int8 GEMV (weights stay int8 in HBM)
-            y = get_ext().w8_gemv(self.qweight, self.scale.view(-1),
-                                  x.reshape(rows, -1).contiguous())
+        route = decode_linear_route(
+            rows, x.shape[-1], torch.int8,
+            use_hip(x) and x.dtype == torch.bfloat16,
+            torch.is_grad_enabled(), decode_gemm_mode())
+        if route != "library":
+            # decode path: the weights stay int8 in HBM
+            x2 = x.reshape(rows, -1).contiguous()
+            scale = self.scale.view(-1)
+            if route == "gemv":
+                y = get_ext().w8_gemv(self.qweight, scale, x2)
+            else:
+                y = get_ext().decode_gemm(self.qweight, x2, scale)
             y = y.view(*x.shape[:-1], self.out_features)
         else:
             w = (self.qweight.to(x.dtype) * self.scale.to(x.dtype))
