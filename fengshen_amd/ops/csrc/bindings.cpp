@@ -74,6 +74,9 @@ void fs_w8_gemv(const void*, const float*, const void*, void*, int, int, int,
                 hipStream_t);
 void fs_decode_gemm(const void*, const float*, const void*, void*, int, int,
                     int, int, hipStream_t);
+int fs_decode_gemm_w4_ksplit(int, int, int);
+void fs_decode_gemm_w4(const void*, const void*, const void*, void*, float*,
+                       int, int, int, int, int, int, hipStream_t);
 void fs_vocab_ce_fwd(const void*, const long*, float*, float*, float*,
                      long, int, int, int, hipStream_t);
 void fs_vocab_ce_bwd(const void*, const long*, const float*, const float*,
@@ -899,6 +902,64 @@ static at::Tensor decode_gemm(at::Tensor w, at::Tensor x,
   return y;
 }
 
+// Split-K MFMA GEMM for int4 weights and 1..16 rows (decode_gemm_w4.hip):
+// qweight uint8 [out_pad/16, K/128, 64, 16] and scales bf16 [K/128, out_pad]
+// as utils/quantize.py: pack_int4 writes them; x [..., K] bf16 with 1..16
+// rows -> y [rows, out] bf16.  ksplit = 0 lets the kernel's rule choose (a
+// function of K and out_pad only); tw = 0 is the default tiles-per-wave
+// build, 1 and 2 pick one.  Allocates y and, for ksplit > 1, the fp32
+// partials, both from the current stream's allocator.
+static at::Tensor decode_gemm_w4(at::Tensor qweight, at::Tensor scales,
+                                 at::Tensor x, int64_t out, int64_t ksplit,
+                                 int64_t tw) {
+  TORCH_CHECK(qweight.scalar_type() == at::kByte && qweight.dim() == 4 &&
+                  qweight.is_contiguous() && qweight.size(0) >= 4 &&
+                  qweight.size(0) % 4 == 0 && qweight.size(1) >= 1 &&
+                  qweight.size(2) == 64 && qweight.size(3) == 16,
+              "decode_gemm_w4: qweight must be contiguous uint8 "
+              "[out_pad/16, K/128, 64, 16] with out_pad a multiple of 64");
+  const int64_t ng = qweight.size(1), out_pad = qweight.size(0) * 16;
+  const int64_t K = ng * 128;
+  TORCH_CHECK(out_pad < (1LL << 31) && K < (1LL << 31),
+              "decode_gemm_w4: out_pad and K must be below 2^31");
+  TORCH_CHECK(scales.scalar_type() == at::kBFloat16 && scales.dim() == 2 &&
+                  scales.is_contiguous() && scales.size(0) == ng &&
+                  scales.size(1) == out_pad,
+              "decode_gemm_w4: scales must be contiguous bf16 [", ng, ", ",
+              out_pad, "]");
+  TORCH_CHECK(out >= 1 && out <= out_pad, "decode_gemm_w4: out must be in 1..",
+              out_pad, ", got ", out);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_contiguous() &&
+                  x.dim() >= 1 && x.size(-1) == K,
+              "decode_gemm_w4: x must be contiguous bf16 [..., ", K, "]");
+  const int64_t rows = x.numel() / K;
+  TORCH_CHECK(rows >= 1 && rows <= 16,
+              "decode_gemm_w4: x must have 1..16 rows, got ", rows);
+  TORCH_CHECK(qweight.is_cuda() && x.is_cuda() && scales.is_cuda() &&
+                  x.device() == qweight.device() &&
+                  scales.device() == qweight.device(),
+              "decode_gemm_w4: qweight, scales and x must be on the same GPU");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(qweight.data_ptr()) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(scales.data_ptr()) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15) == 0,
+              "decode_gemm_w4: qweight, scales and x must be 16-byte aligned");
+  TORCH_CHECK(ksplit >= 0 && ksplit <= ng,
+              "decode_gemm_w4: ksplit must be in 0..K/128 = ", ng, ", got ",
+              ksplit);
+  TORCH_CHECK(tw >= 0 && tw <= 2, "decode_gemm_w4: tw must be 0, 1 or 2");
+  if (ksplit == 0)
+    ksplit = fs_decode_gemm_w4_ksplit((int)K, (int)out_pad, (int)tw);
+  auto y = at::empty({rows, out}, x.options());
+  at::Tensor part;
+  if (ksplit > 1)
+    part = at::empty({ksplit, rows, out_pad}, x.options().dtype(at::kFloat));
+  fs_decode_gemm_w4(qweight.data_ptr(), scales.data_ptr(), x.data_ptr(),
+                    y.data_ptr(), ksplit > 1 ? part.data_ptr<float>() : nullptr,
+                    (int)rows, (int)K, (int)out, (int)out_pad, (int)ksplit,
+                    (int)tw, cur_stream());
+  return y;
+}
+
 // Fused decode step: qkv [b, (nh + 2*nkv)*d] bf16, kc/vc [b, nkv, L, d] bf16
 // caches (written in-place at pos), cos/sin [max_len, d] fp32, pos [1] long.
 // nkv comes from the caches and nh from the width of qkv (nkv == nh: plain
@@ -1159,6 +1220,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("decode_attn", &decode_attn);
   mod.def("decode_gemm", &decode_gemm, py::arg("w"), py::arg("x"),
           py::arg("scale") = py::none());
+  mod.def("decode_gemm_w4", &decode_gemm_w4, py::arg("qweight"),
+          py::arg("scales"), py::arg("x"), py::arg("out"),
+          py::arg("ksplit") = 0, py::arg("tw") = 0);
   mod.def("decode_attn_split", &decode_attn_split, py::arg("qkv"),
           py::arg("kc"), py::arg("vc"), py::arg("cos"), py::arg("sin"),
           py::arg("pos"), py::arg("scale"), py::arg("rope"),

@@ -493,13 +493,22 @@ def decode_linear_route(rows: int, in_features: int, weight_dtype,
     "gemv"         bf16_gemv (bf16 weights, one row) or w8_gemv (int8
                    weights, up to 16 rows): what ran before decode_gemm
     "decode_gemm"  the MFMA weight-streaming kernel, 2..16 rows, K % 64 == 0
-    "library"      F.linear, or the dequantised matmul for int8 weights
+    "decode_gemm_w4"  the split-K MFMA kernel for int4 weights (weight_dtype
+                   torch.uint8, W4Linear), 1..16 rows, K % 128 == 0
+    "library"      F.linear, or the dequantised matmul for int8 and int4
+                   weights
 
     on_gpu means the HIP path is usable for the call (use_hip) and the
     activations are bf16.  mode is FENGSHEN_DECODE_GEMM: "0" never picks
-    decode_gemm, "1" picks it wherever it can run, "auto" from
-    _DECODE_GEMM_MIN_ROWS[weight_dtype] rows.  This is the only place that
-    decides."""
+    decode_gemm or decode_gemm_w4, "1" picks them wherever they can run,
+    "auto" takes decode_gemm from _DECODE_GEMM_MIN_ROWS[weight_dtype] rows
+    and decode_gemm_w4 always (int4 weights have no other kernel).  This is
+    the only place that decides."""
+    if weight_dtype == torch.uint8:
+        if on_gpu and not grad_enabled and 1 <= rows <= 16 and \
+                in_features % 128 == 0 and mode != "0":
+            return "decode_gemm_w4"
+        return "library"
     w8 = weight_dtype == torch.int8
     if not on_gpu or not (w8 or weight_dtype == torch.bfloat16):
         return "library"

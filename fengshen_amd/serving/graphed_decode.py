@@ -27,6 +27,11 @@ hipGraph on ROCm) and replays it per token:
   ops.functional.decode_linear_route.  auto takes it for int8 weights
   (W8Linear) from 4 rows, where it replaces w8_gemv, whose cost grows with
   the batch; bf16 weights keep hipBLASLt, which measured faster;
+- int4 weights (W4Linear, utils.quantize.quantize_model_int4) run
+  decode_gemm_w4 (decode_gemm_w4.hip) for any batch of 1..16: a split-K
+  MFMA kernel that stages x in LDS once per block and streams 4-bit
+  weights with a bf16 scale per 128 input features; its partial-sum buffer
+  comes from the stream's allocator, so the step captures like the others;
 - greedy argmax — or gumbel-max top-k/top-p sampling over a pre-generated
   seeded noise buffer indexed by the step tensor — feeds the token buffer
   consumed by the NEXT replay, so a whole max_new_tokens decode is just N
