@@ -27,6 +27,8 @@ def main():
     p.add_argument("--new_tokens", type=int, default=64)
     p.add_argument("--batch", type=int, default=1)
     p.add_argument("--quant", choices=["bf16", "int8"], default="bf16")
+    p.add_argument("--kv-cache", choices=["bf16", "int8"], default="bf16",
+                   help="KV cache format of the graphed decoder (--graph)")
     p.add_argument("--graph", action="store_true",
                    help="hipGraph-captured decode loop (serving fast path)")
     p.add_argument("--sample", action="store_true",
@@ -66,7 +68,8 @@ def main():
                              max_len=args.prompt_len + args.new_tokens + 8,
                              max_new_tokens=args.new_tokens,
                              do_sample=args.sample, top_k=args.top_k,
-                             top_p=args.top_p, temperature=args.temperature)
+                             top_p=args.top_p, temperature=args.temperature,
+                             kv_cache=args.kv_cache)
         dec.generate(ids, max_new_tokens=4)  # warmup + capture
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -87,6 +90,7 @@ def main():
         "unit": "ms/token",
         "quant": args.quant,
         "graph": bool(args.graph),
+        "kv_cache": args.kv_cache if args.graph else "bf16",
         "batch": args.batch,
         "prompt_len": args.prompt_len,
         "new_tokens": n_new,

@@ -67,6 +67,11 @@ void fs_add_rms_norm(const void*, const void*, const void*, void*, void*,
 void fs_decode_attn_split(const void*, void*, void*, const float*,
                           const float*, const void*, int, float*, void*, int,
                           int, int, int, int, float, int, int, hipStream_t);
+void fs_decode_attn_split_q8(const void*, void*, float*, void*, float*,
+                             const float*, const float*, const void*, int,
+                             float*, void*, int, int, int, int, int, float,
+                             int, int, hipStream_t);
+void fs_kv_quantize_int8(const void*, void*, float*, long, int, hipStream_t);
 void fs_decode_attn(const void*, void*, void*, const float*, const float*,
                     const void*, void*, int, int, int, int, int, float, int,
                     hipStream_t);
@@ -1055,6 +1060,99 @@ static at::Tensor decode_attn_split(at::Tensor qkv, at::Tensor kc,
   return ctx;
 }
 
+// decode_attn_split over an int8 KV cache (decode_attn_q8.hip).  kq/vq are
+// int8 [b, nkv, L, d] with one fp32 scale per row in k_scale/v_scale
+// [b, nkv, L]; row pos_b of all four is written here.  The other arguments
+// and the automatic nsplit are those of decode_attn_split.  L must be a
+// multiple of 4: the kernel reads the scales of 4 keys as one 16-byte load.
+static at::Tensor decode_attn_split_q8(at::Tensor qkv, at::Tensor kq,
+                                       at::Tensor k_scale, at::Tensor vq,
+                                       at::Tensor v_scale, at::Tensor cos_t,
+                                       at::Tensor sin_t, at::Tensor pos,
+                                       double scale, bool rope,
+                                       int64_t nsplit) {
+  TORCH_CHECK(qkv.scalar_type() == at::kBFloat16 && qkv.is_contiguous(),
+              "decode_attn_split_q8: qkv must be contiguous bf16");
+  TORCH_CHECK(kq.dim() == 4 && vq.sizes() == kq.sizes() &&
+                  kq.scalar_type() == at::kChar &&
+                  vq.scalar_type() == at::kChar && kq.is_contiguous() &&
+                  vq.is_contiguous(),
+              "decode_attn_split_q8: caches must be contiguous int8 "
+              "[b, nkv, L, d] of one shape");
+  const int b = kq.size(0), nkv = kq.size(1), L = kq.size(2), d = kq.size(3);
+  TORCH_CHECK(d == 64 || d == 128,
+              "decode_attn_split_q8: head dim must be 64 or 128, got ", d);
+  TORCH_CHECK(b >= 1 && nkv >= 1 && L >= 4 && L % 4 == 0 &&
+                  qkv.numel() % b == 0,
+              "decode_attn_split_q8: cache length must be a positive "
+              "multiple of 4 and qkv [b, ...]");
+  TORCH_CHECK(k_scale.scalar_type() == at::kFloat &&
+                  v_scale.scalar_type() == at::kFloat &&
+                  k_scale.is_contiguous() && v_scale.is_contiguous() &&
+                  k_scale.sizes() == kq.sizes().slice(0, 3) &&
+                  v_scale.sizes() == kq.sizes().slice(0, 3),
+              "decode_attn_split_q8: scales must be contiguous fp32 [", b,
+              ", ", nkv, ", ", L, "]");
+  const int64_t w = qkv.numel() / b - 2 * (int64_t)nkv * d;  // nh * d
+  TORCH_CHECK(w > 0 && w % d == 0 && (w / d) % nkv == 0,
+              "decode_attn_split_q8: qkv must be [b, (nh + 2*nkv)*d] with nh "
+              "a multiple of the caches' ", nkv, " KV heads");
+  const int nh = w / d;
+  TORCH_CHECK(pos.scalar_type() == at::kLong && pos.is_contiguous() &&
+                  (pos.numel() == 1 || pos.numel() == b),
+              "decode_attn_split_q8: pos must be int64 with 1 or ", b,
+              " elements");
+  TORCH_CHECK(cos_t.scalar_type() == at::kFloat &&
+                  sin_t.scalar_type() == at::kFloat && cos_t.dim() == 2 &&
+                  sin_t.sizes() == cos_t.sizes() && cos_t.is_contiguous() &&
+                  sin_t.is_contiguous() && cos_t.size(0) >= L &&
+                  cos_t.size(1) == d,
+              "decode_attn_split_q8: cos/sin must be contiguous fp32 [>= ", L,
+              ", ", d, "]");
+  TORCH_CHECK(nsplit >= 0 && nsplit <= 64,
+              "decode_attn_split_q8: nsplit must be in [0, 64], got ", nsplit);
+  TORCH_CHECK(qkv.is_cuda() && kq.is_cuda() && vq.is_cuda() &&
+                  k_scale.is_cuda() && v_scale.is_cuda() && cos_t.is_cuda() &&
+                  sin_t.is_cuda() && pos.is_cuda(),
+              "decode_attn_split_q8: all tensors must be on the GPU");
+  if (nsplit == 0) {
+    const int64_t blocks = (int64_t)b * nkv * ((nh / nkv + 15) / 16);
+    nsplit = (2 * 256 + blocks - 1) / blocks;
+    nsplit = std::min<int64_t>(nsplit, (L + 255) / 256);
+    nsplit = std::max<int64_t>(std::min<int64_t>(nsplit, 64), 1);
+  }
+  auto ctx = at::empty({b, nh * d}, qkv.options());
+  at::Tensor ws;
+  if (nsplit > 1)
+    ws = at::empty({b, nh, nsplit, d + 2}, qkv.options().dtype(at::kFloat));
+  fs_decode_attn_split_q8(qkv.data_ptr(), kq.data_ptr(),
+                          k_scale.data_ptr<float>(), vq.data_ptr(),
+                          v_scale.data_ptr<float>(), cos_t.data_ptr<float>(),
+                          sin_t.data_ptr<float>(), pos.data_ptr(),
+                          (int)pos.numel(),
+                          nsplit > 1 ? ws.data_ptr<float>() : nullptr,
+                          ctx.data_ptr(), b, nh, nkv, d, L, (float)scale,
+                          rope ? 1 : 0, (int)nsplit, cur_stream());
+  return ctx;
+}
+
+// x bf16 [..., d], d 64 or 128 -> (q int8 [..., d], scale fp32 [...]): the
+// row quantisation of the int8 KV cache (decode_attn_q8.hip).
+static std::vector<at::Tensor> kv_quantize_int8(at::Tensor x) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
+                  x.is_contiguous() && x.dim() >= 1,
+              "kv_quantize_int8: x must be a contiguous bf16 GPU tensor");
+  const int d = x.size(-1);
+  TORCH_CHECK(d == 64 || d == 128,
+              "kv_quantize_int8: last dim must be 64 or 128, got ", d);
+  auto q = at::empty(x.sizes(), x.options().dtype(at::kChar));
+  auto sc = at::empty(x.sizes().slice(0, x.dim() - 1),
+                      x.options().dtype(at::kFloat));
+  fs_kv_quantize_int8(x.data_ptr(), q.data_ptr(), sc.data_ptr<float>(),
+                      (long)(x.numel() / d), d, cur_stream());
+  return {q, sc};
+}
+
 // a,b [rows, H] bf16 -> (sum=a+b, y=rmsnorm(sum)*w), inference-only
 static std::vector<at::Tensor> add_rms_norm(at::Tensor a, at::Tensor b,
                                             at::Tensor w, double eps) {
@@ -1227,6 +1325,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("kc"), py::arg("vc"), py::arg("cos"), py::arg("sin"),
           py::arg("pos"), py::arg("scale"), py::arg("rope"),
           py::arg("nsplit") = 0);
+  mod.def("decode_attn_split_q8", &decode_attn_split_q8, py::arg("qkv"),
+          py::arg("kq"), py::arg("k_scale"), py::arg("vq"),
+          py::arg("v_scale"), py::arg("cos"), py::arg("sin"), py::arg("pos"),
+          py::arg("scale"), py::arg("rope"), py::arg("nsplit") = 0);
+  mod.def("kv_quantize_int8", &kv_quantize_int8);
   mod.def("add_rms_norm", &add_rms_norm);
   mod.def("flash_attn_fwd", &flash_attn_fwd);
   mod.def("vocab_ce_fwd", [](at::Tensor logits2d, at::Tensor targets,

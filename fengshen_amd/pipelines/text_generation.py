@@ -45,7 +45,8 @@ class Pipeline(BasePipeline):
 
     def __init__(self, args=None, model=None, tokenizer=None,
                  use_graph: bool = True, max_len: int = 1024,
-                 max_new_tokens: int = 256, **kwargs):
+                 max_new_tokens: int = 256, kv_cache: str = "bf16",
+                 **kwargs):
         if isinstance(model, str):
             from transformers import AutoModelForCausalLM, AutoTokenizer
             if tokenizer is None:
@@ -57,6 +58,7 @@ class Pipeline(BasePipeline):
         self.use_graph = use_graph
         self.max_len = max_len
         self.max_new_tokens = max_new_tokens
+        self.kv_cache = kv_cache  # "bf16" | "int8", see GraphedDecoder
         self._decoder = None
         self._decoder_key = None
 
@@ -83,12 +85,13 @@ class Pipeline(BasePipeline):
         from fengshen_amd.serving.graphed_decode import GraphedDecoder
         # top_k changes the captured graph shape; temperature/top_p are
         # device scalars and can be retuned on the live decoder.
-        key = (do_sample, top_k, batch)
+        key = (do_sample, top_k, batch, self.kv_cache)
         if self._decoder is None or self._decoder_key != key:
             self._decoder = GraphedDecoder(
                 self.model, batch=batch, max_len=self.max_len,
                 max_new_tokens=self.max_new_tokens, do_sample=do_sample,
-                top_k=top_k, top_p=top_p, temperature=temperature)
+                top_k=top_k, top_p=top_p, temperature=temperature,
+                kv_cache=self.kv_cache)
             self._decoder_key = key
         else:
             self._decoder.top_p.fill_(float(top_p))

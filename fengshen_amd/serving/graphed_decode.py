@@ -32,6 +32,14 @@ hipGraph on ROCm) and replays it per token:
   MFMA kernel that stages x in LDS once per block and streams 4-bit
   weights with a bf16 scale per 128 input features; its partial-sum buffer
   comes from the stream's allocator, so the step captures like the others;
+- kv_cache="int8" keeps K and V as int8 with one fp32 scale per cached row
+  (k_scale / v_scale [b, kv_heads, max_len]) and runs decode_attn_split_q8
+  (decode_attn_q8.hip), the split kernel reading half the bytes; prefill
+  quantises its K/V with kv_quantize_int8, each step quantises its own row
+  and attends to the quantised values.  Head dim 64 or 128, max_len a
+  multiple of 4, the split kernel only; anything else raises ValueError,
+  there is no fallback to a bf16 cache.  Per-row scales do not isolate the
+  per-channel outliers K has in real models;
 - greedy argmax — or gumbel-max top-k/top-p sampling over a pre-generated
   seeded noise buffer indexed by the step tensor — feeds the token buffer
   consumed by the NEXT replay, so a whole max_new_tokens decode is just N
@@ -91,7 +99,11 @@ class GraphedDecoder:
     def __init__(self, model, batch: int = 1, max_len: int = 512,
                  max_new_tokens: int = 256, do_sample: bool = False,
                  top_k: int = 0, top_p: float = 1.0,
-                 temperature: float = 1.0):
+                 temperature: float = 1.0, kv_cache: str = "bf16"):
+        if kv_cache not in ("bf16", "int8"):
+            raise ValueError(
+                f"kv_cache must be 'bf16' or 'int8', got {kv_cache!r}")
+        self.kv_cache = kv_cache
         self.model = model.eval()
         cfg = model.config
         dev = next(model.parameters()).device
@@ -108,11 +120,17 @@ class GraphedDecoder:
         self.nh, self.nkv, self.hd = nh, nkv, hd
         self.scale = 1.0 / math.sqrt(hd)
 
-        # static state
+        # static state; kv_cache="int8": int8 rows and one fp32 scale per row
+        cdt = torch.int8 if kv_cache == "int8" else dt
         self.k_cache = [torch.zeros(batch, nkv, max_len, hd, device=dev,
-                                    dtype=dt) for _ in range(L)]
+                                    dtype=cdt) for _ in range(L)]
         self.v_cache = [torch.zeros(batch, nkv, max_len, hd, device=dev,
-                                    dtype=dt) for _ in range(L)]
+                                    dtype=cdt) for _ in range(L)]
+        if kv_cache == "int8":
+            self.k_scale = [torch.zeros(batch, nkv, max_len, device=dev)
+                            for _ in range(L)]
+            self.v_scale = [torch.zeros(batch, nkv, max_len, device=dev)
+                            for _ in range(L)]
         self.tok = torch.zeros(batch, 1, device=dev, dtype=torch.long)
         # one position per sequence; decode_attn and the eager step share
         # one position and read the [1] view self.pos[:1]
@@ -155,6 +173,18 @@ class GraphedDecoder:
             and dt == torch.bfloat16
             and os.environ.get("FENGSHEN_AMD_FORCE_EAGER") != "1"
             and os.environ.get("FENGSHEN_DECODE_FUSED", "1") == "1")
+        if kv_cache == "int8":
+            if not self._fused_attn or self._split_mode == "0":
+                raise ValueError(
+                    "kv_cache='int8' needs the fused decode_attn_split_q8 "
+                    "kernel: a GPU, bf16 weights, the HIP extension, "
+                    "FENGSHEN_DECODE_FUSED not 0 and FENGSHEN_DECODE_SPLIT "
+                    "not 0")
+            if hd not in (64, 128) or max_len % 4:
+                raise ValueError(
+                    "kv_cache='int8' serves head dim 64 or 128 and a max_len "
+                    f"that is a multiple of 4, got {hd} and {max_len}")
+            self._use_split = True
         self._graph: Optional[torch.cuda.CUDAGraph] = None
 
     @property
@@ -211,10 +241,17 @@ class GraphedDecoder:
                 qkv = layer.attention.qkv_proj(x)
                 if isinstance(qkv, tuple):
                     qkv = qkv[0]
-                ctx = attn(
-                    qkv.view(b, (nh + 2 * nkv) * hd), self.k_cache[i],
-                    self.v_cache[i], self.cos, self.sin, pos,
-                    self.scale, bool(layer.attention.rotary))
+                if self.kv_cache == "int8":
+                    ctx = self._ext.decode_attn_split_q8(
+                        qkv.view(b, (nh + 2 * nkv) * hd), self.k_cache[i],
+                        self.k_scale[i], self.v_cache[i], self.v_scale[i],
+                        self.cos, self.sin, pos, self.scale,
+                        bool(layer.attention.rotary))
+                else:
+                    ctx = attn(
+                        qkv.view(b, (nh + 2 * nkv) * hd), self.k_cache[i],
+                        self.v_cache[i], self.cos, self.sin, pos,
+                        self.scale, bool(layer.attention.rotary))
                 out = layer.attention.out_proj(ctx.view(b, 1, nh * hd))
                 if isinstance(out, tuple):
                     out = out[0]
@@ -313,6 +350,9 @@ class GraphedDecoder:
         for i in range(len(self.k_cache)):
             layer_cache = cache.layers[i]  # transformers >= 5 DynamicCache
             k, v = layer_cache.keys, layer_cache.values
+            if self.kv_cache == "int8":
+                self._fill_int8(i, k, v, prompt_lens)
+                continue
             self.k_cache[i][:, :, :plen].copy_(k)
             self.v_cache[i][:, :, :plen].copy_(v)
             self.k_cache[i][:, :, plen:].zero_()
@@ -326,6 +366,22 @@ class GraphedDecoder:
             last = out.logits[torch.arange(self.batch, device=self.dev),
                               prompt_lens - 1]
         self.tok.copy_(self._pick(last, self.step_i))
+
+    def _fill_int8(self, i, k, v, prompt_lens):
+        """Quantise the prefilled K/V [b, nkv, plen, hd] of layer i into the
+        int8 cache; rows at and above a sequence's prompt length get zero
+        int8 and zero scale."""
+        plen = k.shape[2]
+        lens = (prompt_lens if prompt_lens is not None
+                else self.pos.new_full((self.batch,), plen))
+        keep = (self.ar[:plen] < lens[:, None])[:, None]  # [b, 1, plen]
+        for x, cache, scale in ((k, self.k_cache[i], self.k_scale[i]),
+                                (v, self.v_cache[i], self.v_scale[i])):
+            q, s = self._ext.kv_quantize_int8(x.contiguous())
+            cache.zero_()
+            scale.zero_()
+            cache[:, :, :plen].copy_(q * keep[..., None])
+            scale[:, :, :plen].copy_(s * keep)
 
     def _capture(self):
         # warm up twice on a side stream (allocator + kernels), then capture

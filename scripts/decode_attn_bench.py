@@ -1,15 +1,20 @@
 """decode_attn (one block per head, serial over the prefix) against
-decode_attn_split (split-KV, grouped heads) on the same tensors, and the
-end-to-end ms/token of GraphedDecoder with either kernel.
+decode_attn_split (split-KV, grouped heads) on the same tensors and
+decode_attn_split_q8 on their int8 quantisation (head dim 64 / 128), and the
+end-to-end ms/token of GraphedDecoder with either kernel and, with
+--kv-cache int8, with the int8 cache.
 
     python scripts/decode_attn_bench.py            # every step
     python scripts/decode_attn_bench.py --step 1   # one step, in-process
 
 Every step runs in a child process of its own under a time limit; the first
 step that fails ends the script.  Times are device events around ITERS
-back-to-back calls; the two kernels alternate inside each of 5 repeats after a
+back-to-back calls; the kernels alternate inside each of 5 repeats after a
 warm-up, and the table gives median [min, max] per call.  K/V GB/s counts
 2 * (pos + 1) * h_kv * d * 2 * b bytes; the floor is those bytes at 6.3 TB/s.
+The int8 kernel's GB/s counts what it reads, 2 * (pos + 1) * h_kv * (d + 4)
+* b bytes (rows and their fp32 scales), and "% floor" is the time those bytes
+take at 6.3 TB/s over the measured time.
 """
 import argparse
 import math
@@ -21,7 +26,8 @@ import sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)),
                                 ".."))
 
-SHAPES = [(40, 40, 128), (32, 8, 128), (32, 1, 128), (36, 36, 96)]
+SHAPES = [(40, 40, 128), (32, 8, 128), (32, 1, 128), (36, 36, 96),
+          (4, 4, 64)]
 BATCHES = [1, 8]
 POSITIONS = [511, 2047, 8191, 32767]
 REPEATS, ITERS = 5, 20
@@ -54,8 +60,9 @@ def kernel_step(idx):
     scale = 1 / math.sqrt(d)
     print(f"## h={h} h_kv={h_kv} d={d}   (us per call: median [min, max])")
     print("| b | pos | floor us | decode_attn | GB/s | decode_attn_split "
-          "| GB/s | max abs diff |")
-    print("|---|---|---|---|---|---|---|---|")
+          "| GB/s | max abs diff | decode_attn_split_q8 | GB/s | % floor | "
+          "max abs diff to split |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|")
     for b in BATCHES:
         for p in POSITIONS:
             L = p + 1
@@ -77,16 +84,26 @@ def kernel_step(idx):
             def old():
                 return ext.decode_attn(qkv, kc, vc, cos, sin, pos1, scale,
                                        True)
-            has_old = d in (64, 128)
-            diff = float("nan")
+            has_old = d in (64, 128)  # and the int8 kernel
+            diff = diff8 = float("nan")
             if has_old:
+                kq, ks = ext.kv_quantize_int8(kc)
+                vq, vs = ext.kv_quantize_int8(vc)
+                nbytes8 = 2 * (p + 1) * h_kv * (d + 4) * b
+
+                def q8():
+                    return ext.decode_attn_split_q8(qkv, kq, ks, vq, vs, cos,
+                                                    sin, posb, scale, True)
                 diff = float((old().float() - new().float()).abs().max())
+                diff8 = float((q8().float() - new().float()).abs().max())
                 _time(old)
+                _time(q8)
             _time(new)
-            t_old, t_new = [], []
+            t_old, t_new, t_q8 = [], [], []
             for _ in range(REPEATS):
                 if has_old:
                     t_old.append(_time(old))
+                    t_q8.append(_time(q8))
                 t_new.append(_time(new))
             o = (f"{_fmt(t_old)} | "
                  f"{nbytes / statistics.median(t_old) / 1e3:6.0f}"
@@ -94,13 +111,19 @@ def kernel_step(idx):
             print(f"| {b} | {p} | {nbytes / HBM_BPS * 1e6:6.1f} | {o} | "
                   f"{_fmt(t_new)} | "
                   f"{nbytes / statistics.median(t_new) / 1e3:6.0f} | "
-                  f"{diff:.4f} |", flush=True)
+                  f"{diff:.4f} | " + (
+                      f"{_fmt(t_q8)} | "
+                      f"{nbytes8 / statistics.median(t_q8) / 1e3:6.0f} | "
+                      f"{nbytes8 / HBM_BPS * 1e8 / statistics.median(t_q8):4.0f}"
+                      f" | {diff8:.4f} |" if has_old else "- | - | - | - |"),
+                  flush=True)
             del qkv, kc, vc
 
 
-def e2e_step():
+def e2e_step(kv_cache="bf16", batch=1):
     """4 layers of the Ziya-13B layer shape, max_len 8192, 4096-token prompt:
-    ms/token of the captured step with FENGSHEN_DECODE_SPLIT=0 and =1."""
+    ms/token of the captured step with FENGSHEN_DECODE_SPLIT=0 and =1, and
+    with kv_cache "int8" a third decoder with the int8 cache, alternating."""
     import torch
     from fengshen_amd.models.llama.configuration_llama import LlamaConfig
     from fengshen_amd.models.llama.modeling_llama import LlamaForCausalLM
@@ -110,14 +133,18 @@ def e2e_step():
                       num_hidden_layers=4, num_attention_heads=40,
                       intermediate_size=13824, max_position_embeddings=8192)
     model = LlamaForCausalLM(cfg).to(torch.bfloat16).cuda().eval()
-    ids = torch.randint(3, 39424, (1, 4096), device="cuda")
+    ids = torch.randint(3, 39424, (batch, 4096), device="cuda")
     decs = {}
-    for mode in ("0", "1"):
-        os.environ["FENGSHEN_DECODE_SPLIT"] = mode
-        decs[mode] = GraphedDecoder(model, batch=1, max_len=8192,
-                                    max_new_tokens=64)
+    runs = [("0", "bf16"), ("1", "bf16")]
+    if kv_cache == "int8":
+        runs.append(("1", "int8"))
+    for split, kv in runs:
+        os.environ["FENGSHEN_DECODE_SPLIT"] = split
+        mode = f"{split} kv_cache={kv}"
+        decs[mode] = GraphedDecoder(model, batch=batch, max_len=8192,
+                                    max_new_tokens=64, kv_cache=kv)
         decs[mode].generate(ids, max_new_tokens=8)  # capture + warm-up
-    times = {"0": [], "1": []}
+    times = {mode: [] for mode in decs}
     for _ in range(REPEATS):
         for mode, dec in decs.items():
             dec._prefill(ids)
@@ -130,22 +157,34 @@ def e2e_step():
             end.synchronize()
             times[mode].append(beg.elapsed_time(end) / 48)
     for mode, ts in times.items():
-        print(f"GraphedDecoder 4 layers, pos 4096.., FENGSHEN_DECODE_SPLIT="
-              f"{mode}: {statistics.median(ts):.3f} ms/token "
-              f"[{min(ts):.3f}, {max(ts):.3f}]", flush=True)
+        dec = decs[mode]
+        cache = dec.k_cache + dec.v_cache + (
+            dec.k_scale + dec.v_scale if dec.kv_cache == "int8" else [])
+        print(f"GraphedDecoder 4 layers, batch {batch}, pos 4096.., "
+              f"FENGSHEN_DECODE_SPLIT={mode}: {statistics.median(ts):.3f} "
+              f"ms/token [{min(ts):.3f}, {max(ts):.3f}], cache "
+              f"{sum(t.numel() * t.element_size() for t in cache) / 2**20:.0f}"
+              " MiB", flush=True)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--step", type=int, default=None,
-                    help="0..3: kernel table of SHAPES[step]; 4: end to end")
+                    help="0..4: kernel table of SHAPES[step]; 5: end to end")
+    ap.add_argument("--kv-cache", choices=["bf16", "int8"], default="bf16",
+                    help="end to end: int8 adds a decoder with the int8 cache")
+    ap.add_argument("--batch", type=int, default=1, help="end to end batch")
     args = ap.parse_args()
     if args.step is not None:
-        e2e_step() if args.step == len(SHAPES) else kernel_step(args.step)
+        if args.step == len(SHAPES):
+            e2e_step(args.kv_cache, args.batch)
+        else:
+            kernel_step(args.step)
         return 0
     for step in range(len(SHAPES) + 1):
         rc = subprocess.run([sys.executable, os.path.abspath(__file__),
-                             "--step", str(step)],
+                             "--step", str(step), "--kv-cache", args.kv_cache,
+                             "--batch", str(args.batch)],
                             timeout=STEP_TIMEOUT).returncode
         if rc != 0:
             print(f"step {step} failed with exit status {rc}; stopping")
