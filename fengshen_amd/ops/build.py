@@ -26,6 +26,7 @@ def sources():
             os.path.join(_CSRC, "sparse_flash.hip"),
             os.path.join(_CSRC, "decode_attn.hip"),
             os.path.join(_CSRC, "decode_attn_q8.hip"),
+            os.path.join(_CSRC, "decode_attn_mt.hip"),
             os.path.join(_CSRC, "decode_gemm.hip"),
             os.path.join(_CSRC, "decode_gemm_w4.hip")]
     fa = os.path.join(_CSRC, "flash_attn.hip")

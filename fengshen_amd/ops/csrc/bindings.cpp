@@ -67,6 +67,10 @@ void fs_add_rms_norm(const void*, const void*, const void*, void*, void*,
 void fs_decode_attn_split(const void*, void*, void*, const float*,
                           const float*, const void*, int, float*, void*, int,
                           int, int, int, int, float, int, int, hipStream_t);
+void fs_decode_attn_split_mt(const void*, void*, void*, const float*,
+                             const float*, const void*, int, float*, void*,
+                             int, int, int, int, int, int, float, int, int,
+                             hipStream_t);
 void fs_decode_attn_split_q8(const void*, void*, float*, void*, float*,
                              const float*, const float*, const void*, int,
                              float*, void*, int, int, int, int, int, float,
@@ -1003,10 +1007,18 @@ static at::Tensor decode_attn(at::Tensor qkv, at::Tensor kc, at::Tensor vc,
 // The automatic count depends on shapes only, so a captured graph keeps it:
 // the smallest nsplit that gives the grid two blocks per CU (256 CUs), capped
 // at ceil(L / 256) and at 64.
+// tokens = T in [2, 16] is the multi-token step (decode_attn_mt.hip): qkv is
+// [b, T, (nh + 2*nkv)*d], token t of sequence b sits at pos_b + t, rows
+// pos_b .. pos_b+T-1 of the caches are written, pos is clamped into
+// [0, L - T] and the result is [b, T, nh*d].  The automatic nsplit counts
+// ceil(T*G/16) column groups per KV head.  tokens = 1 is the call above.
 static at::Tensor decode_attn_split(at::Tensor qkv, at::Tensor kc,
                                     at::Tensor vc, at::Tensor cos_t,
                                     at::Tensor sin_t, at::Tensor pos,
-                                    double scale, bool rope, int64_t nsplit) {
+                                    double scale, bool rope, int64_t nsplit,
+                                    int64_t tokens) {
+  TORCH_CHECK(tokens >= 1 && tokens <= 16,
+              "decode_attn_split: tokens must be in [1, 16], got ", tokens);
   TORCH_CHECK(qkv.scalar_type() == at::kBFloat16 && qkv.is_contiguous(),
               "decode_attn_split: qkv must be contiguous bf16");
   TORCH_CHECK(kc.dim() == 4 && vc.sizes() == kc.sizes() &&
@@ -1018,9 +1030,17 @@ static at::Tensor decode_attn_split(at::Tensor qkv, at::Tensor kc,
   const int b = kc.size(0), nkv = kc.size(1), L = kc.size(2), d = kc.size(3);
   TORCH_CHECK(d == 64 || d == 96 || d == 128,
               "decode_attn_split: head dim must be 64/96/128, got ", d);
-  TORCH_CHECK(b >= 1 && nkv >= 1 && L >= 1 && qkv.numel() % b == 0,
+  TORCH_CHECK(b >= 1 && nkv >= 1 && L >= 1 &&
+                  qkv.numel() % (b * tokens) == 0,
               "decode_attn_split: empty cache or qkv not [b, ...]");
-  const int64_t w = qkv.numel() / b - 2 * (int64_t)nkv * d;  // nh * d
+  TORCH_CHECK(tokens == 1 ||
+                  (qkv.dim() == 3 && qkv.size(0) == b &&
+                   qkv.size(1) == tokens && L >= tokens),
+              "decode_attn_split: tokens = ", tokens, " needs qkv [", b, ", ",
+              tokens, ", (nh + 2*nkv)*d] and a cache of at least ", tokens,
+              " rows");
+  // nh * d, per token
+  const int64_t w = qkv.numel() / (b * tokens) - 2 * (int64_t)nkv * d;
   TORCH_CHECK(w > 0 && w % d == 0 && (w / d) % nkv == 0,
               "decode_attn_split: qkv must be [b, (nh + 2*nkv)*d] with nh a "
               "multiple of the caches' ", nkv, " KV heads");
@@ -1042,10 +1062,26 @@ static at::Tensor decode_attn_split(at::Tensor qkv, at::Tensor kc,
                   cos_t.is_cuda() && sin_t.is_cuda() && pos.is_cuda(),
               "decode_attn_split: all tensors must be on the GPU");
   if (nsplit == 0) {
-    const int64_t blocks = (int64_t)b * nkv * ((nh / nkv + 15) / 16);
+    const int64_t blocks =
+        (int64_t)b * nkv * ((tokens * (nh / nkv) + 15) / 16);
     nsplit = (2 * 256 + blocks - 1) / blocks;
     nsplit = std::min<int64_t>(nsplit, (L + 255) / 256);
     nsplit = std::max<int64_t>(std::min<int64_t>(nsplit, 64), 1);
+  }
+  if (tokens > 1) {
+    auto ctx = at::empty({b, tokens, nh * d}, qkv.options());
+    at::Tensor ws;
+    if (nsplit > 1)
+      ws = at::empty({b, tokens, nh, nsplit, d + 2},
+                     qkv.options().dtype(at::kFloat));
+    fs_decode_attn_split_mt(qkv.data_ptr(), kc.data_ptr(), vc.data_ptr(),
+                            cos_t.data_ptr<float>(), sin_t.data_ptr<float>(),
+                            pos.data_ptr(), (int)pos.numel(),
+                            nsplit > 1 ? ws.data_ptr<float>() : nullptr,
+                            ctx.data_ptr(), b, (int)tokens, nh, nkv, d, L,
+                            (float)scale, rope ? 1 : 0, (int)nsplit,
+                            cur_stream());
+    return ctx;
   }
   auto ctx = at::empty({b, nh * d}, qkv.options());
   at::Tensor ws;
@@ -1324,7 +1360,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("decode_attn_split", &decode_attn_split, py::arg("qkv"),
           py::arg("kc"), py::arg("vc"), py::arg("cos"), py::arg("sin"),
           py::arg("pos"), py::arg("scale"), py::arg("rope"),
-          py::arg("nsplit") = 0);
+          py::arg("nsplit") = 0, py::arg("tokens") = 1);
   mod.def("decode_attn_split_q8", &decode_attn_split_q8, py::arg("qkv"),
           py::arg("kq"), py::arg("k_scale"), py::arg("vq"),
           py::arg("v_scale"), py::arg("cos"), py::arg("sin"), py::arg("pos"),

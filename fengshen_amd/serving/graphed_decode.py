@@ -40,6 +40,16 @@ hipGraph on ROCm) and replays it per token:
   multiple of 4, the split kernel only; anything else raises ValueError,
   there is no fallback to a bf16 cache.  Per-row scales do not isolate the
   per-channel outliers K has in real models;
+- lookahead=T (2..16) makes the captured step a T-token verify step of
+  greedy lookahead decoding: the last accepted token and T-1 drafts go
+  through the layers as [b, T, H] rows, attention is one
+  decode_attn_split(..., tokens=T) launch per layer (decode_attn_mt.hip,
+  the T tokens share one pass over the cache), and the longest prefix of
+  drafts that equals the model's own argmax is accepted, so a replay emits
+  1..T tokens per sequence and the output is the greedy output.  Drafts are
+  a bigram lookup over the sequence's own tokens (generate(hint_ids=...)
+  puts a guess of the continuation in front of them); no draft model.
+  bf16 cache, greedy and the split kernel only;
 - greedy argmax — or gumbel-max top-k/top-p sampling over a pre-generated
   seeded noise buffer indexed by the step tensor — feeds the token buffer
   consumed by the NEXT replay, so a whole max_new_tokens decode is just N
@@ -99,7 +109,8 @@ class GraphedDecoder:
     def __init__(self, model, batch: int = 1, max_len: int = 512,
                  max_new_tokens: int = 256, do_sample: bool = False,
                  top_k: int = 0, top_p: float = 1.0,
-                 temperature: float = 1.0, kv_cache: str = "bf16"):
+                 temperature: float = 1.0, kv_cache: str = "bf16",
+                 lookahead: int = 1):
         if kv_cache not in ("bf16", "int8"):
             raise ValueError(
                 f"kv_cache must be 'bf16' or 'int8', got {kv_cache!r}")
@@ -131,13 +142,31 @@ class GraphedDecoder:
                             for _ in range(L)]
             self.v_scale = [torch.zeros(batch, nkv, max_len, device=dev)
                             for _ in range(L)]
-        self.tok = torch.zeros(batch, 1, device=dev, dtype=torch.long)
+        if not 1 <= lookahead <= 16:
+            raise ValueError(f"lookahead must be in [1, 16], got {lookahead}")
+        self.lookahead = lookahead
+        self.last_replays = 0  # graph replays of the last generate()
+        # the last accepted token, then lookahead - 1 drafts
+        self.tok = torch.zeros(batch, lookahead, device=dev,
+                               dtype=torch.long)
         # one position per sequence; decode_attn and the eager step share
         # one position and read the [1] view self.pos[:1]
         self.pos = torch.zeros(batch, device=dev, dtype=torch.long)
         self.step_i = torch.zeros(1, device=dev, dtype=torch.long)
-        self.out_tokens = torch.zeros(batch, max_new_tokens, device=dev,
+        # a lookahead step writes all its T predictions at the row's count
+        self.out_tokens = torch.zeros(
+            batch, max_new_tokens + (lookahead if lookahead > 1 else 0),
+            device=dev, dtype=torch.long)
+        if lookahead > 1:
+            # tokens emitted per sequence; the draft corpus of a row is
+            # [hint | prompt | accepted tokens], sequence position p at
+            # column hint_n + p, so it ends at column hint_n + pos
+            self.count = torch.zeros(batch, device=dev, dtype=torch.long)
+            self.corpus = torch.zeros(batch, 2 * max_len, device=dev,
                                       dtype=torch.long)
+            self.hint_n = torch.zeros(1, device=dev, dtype=torch.long)
+            self.ar_t = torch.arange(lookahead, device=dev)
+            self.ar_c = torch.arange(2 * max_len, device=dev)
         self.ar = torch.arange(max_len, device=dev)
         cos, sin = F_ops.build_rope_cache(
             max_len, hd, base=getattr(cfg, "rotary_emb_base",
@@ -185,6 +214,20 @@ class GraphedDecoder:
                     "kv_cache='int8' serves head dim 64 or 128 and a max_len "
                     f"that is a multiple of 4, got {hd} and {max_len}")
             self._use_split = True
+        if lookahead > 1:
+            if not self._fused_attn or self._split_mode == "0":
+                raise ValueError(
+                    "lookahead > 1 needs the fused decode_attn_split kernel: "
+                    "a GPU, bf16 weights, head dim 64/96/128, the HIP "
+                    "extension, FENGSHEN_DECODE_FUSED not 0 and "
+                    "FENGSHEN_DECODE_SPLIT not 0")
+            if kv_cache != "bf16":
+                raise ValueError("lookahead > 1 needs kv_cache='bf16': the "
+                                 "multi-token kernel reads bf16 caches only")
+            if do_sample:
+                raise ValueError("lookahead > 1 needs do_sample=False: "
+                                 "drafts are verified against the argmax")
+            self._use_split = True  # forced, as ragged prompts force it
         self._graph: Optional[torch.cuda.CUDAGraph] = None
 
     @property
@@ -211,15 +254,17 @@ class GraphedDecoder:
         return s, norm(s)
 
     def _step(self):
-        """Graph-safe single-token decode; advances tok/pos/step_i."""
+        """Graph-safe decode step; advances tok/pos/step_i (lookahead > 1:
+        tok/pos/count by the tokens it accepted)."""
         m = self.model.model
         b, nh, nkv, hd = self.batch, self.nh, self.nkv, self.hd
+        T = self.lookahead
         # per-sequence positions for decode_attn_split, else the shared one
         split = self._fused_attn and self._use_split
         pos = self.pos if split else self.pos[:1]
         attn = (self._ext.decode_attn_split if split
                 else self._ext.decode_attn) if self._fused_attn else None
-        h = m.embed_tokens(self.tok)  # [b, 1, H]
+        h = m.embed_tokens(self.tok)  # [b, T, H]
         if not self._fused_attn:
             c = self.cos.index_select(0, pos).to(self.dt)  # [1, hd]
             s = self.sin.index_select(0, pos).to(self.dt)
@@ -247,12 +292,17 @@ class GraphedDecoder:
                         self.k_scale[i], self.v_cache[i], self.v_scale[i],
                         self.cos, self.sin, pos, self.scale,
                         bool(layer.attention.rotary))
+                elif T > 1:
+                    ctx = attn(
+                        qkv.view(b, T, (nh + 2 * nkv) * hd), self.k_cache[i],
+                        self.v_cache[i], self.cos, self.sin, pos,
+                        self.scale, bool(layer.attention.rotary), tokens=T)
                 else:
                     ctx = attn(
                         qkv.view(b, (nh + 2 * nkv) * hd), self.k_cache[i],
                         self.v_cache[i], self.cos, self.sin, pos,
                         self.scale, bool(layer.attention.rotary))
-                out = layer.attention.out_proj(ctx.view(b, 1, nh * hd))
+                out = layer.attention.out_proj(ctx.view(b, T, nh * hd))
                 if isinstance(out, tuple):
                     out = out[0]
                 h, x = self._add_norm(h, out, layer.post_attention_norm)
@@ -261,7 +311,10 @@ class GraphedDecoder:
                     mlp = mlp[0]
                 pend = (h, mlp)
             _, h = self._add_norm(pend[0], pend[1], m.norm)
-            self._emit(h)
+            if T > 1:
+                self._emit_lookahead(h)
+            else:
+                self._emit(h)
             return
         for i, layer in enumerate(m.layers):
             res = h
@@ -310,6 +363,45 @@ class GraphedDecoder:
         self.tok.copy_(nxt)
         self.pos.add_(1)
         self.step_i.add_(1)
+
+    def _draft(self):
+        """tok[:, 1:] = the T - 1 tokens that followed the most recent earlier
+        occurrence of the row's last two tokens in its corpus, or token 0
+        where there is none.  Torch ops on static shapes: graph-safe."""
+        end = (self.hint_n + self.pos)[:, None]  # column of the last token
+        last = self.corpus.gather(1, torch.cat([end - 1, end], 1))
+        hit = ((self.corpus == last[:, 1:])
+               & (self.corpus.roll(1, 1) == last[:, :1])
+               & (self.ar_c >= 1) & (self.ar_c < end))
+        at = (hit * self.ar_c).amax(1, keepdim=True)  # 0: no occurrence
+        # columns past the end hold junk of earlier steps; as drafts they
+        # are merely wrong
+        nxt = self.corpus.gather(
+            1, (at + self.ar_t[1:]).clamp(max=self.corpus.shape[1] - 1))
+        self.tok[:, 1:] = nxt * (at > 0)
+
+    def _emit_lookahead(self, h):
+        """lm_head over the T rows -> accept the longest prefix of drafts
+        that equals the predictions -> record n_acc + 1 tokens per sequence,
+        advance pos/count by as many, draft for the next step."""
+        T = self.lookahead
+        logits = self.model.lm_head(h)
+        if isinstance(logits, tuple):
+            logits = logits[0]
+        pred = logits.argmax(dim=-1)  # [b, T]: the token after tok[:, t]
+        ok = (self.tok[:, 1:] == pred[:, :-1]).long().cumprod(1).sum(1)
+        # never past max_new tokens: keeps pos inside the window while the
+        # other sequences finish
+        adv = torch.minimum(ok + 1, self.max_new - self.count)
+        # all T predictions go out; those past adv lie at and above the new
+        # count / corpus end and the next step overwrites them
+        self.out_tokens.scatter_(1, self.count[:, None] + self.ar_t, pred)
+        self.corpus.scatter_(
+            1, (self.hint_n + self.pos + 1)[:, None] + self.ar_t, pred)
+        self.tok[:, :1] = pred.gather(1, (adv - 1).clamp(min=0)[:, None])
+        self.pos.add_(adv)
+        self.count.add_(adv)
+        self._draft()
 
     def _pick(self, last_logits: torch.Tensor,
               step: torch.Tensor) -> torch.Tensor:
@@ -401,7 +493,8 @@ class GraphedDecoder:
     def generate(self, prompt_ids: torch.Tensor,
                  max_new_tokens: Optional[int] = None,
                  eos_token_id: Optional[int] = None,
-                 prompt_lens: Optional[torch.Tensor] = None):
+                 prompt_lens: Optional[torch.Tensor] = None,
+                 hint_ids: Optional[torch.Tensor] = None):
         """Greedy (or sampled) decode via graph replays.
 
         Without prompt_lens all prompts have the length of prompt_ids and
@@ -411,8 +504,20 @@ class GraphedDecoder:
         row i holds prompt_lens[i] real tokens.  The result is then a list
         of b 1-D tensors, row i being its prompt_lens[i] prompt tokens
         followed by its n new tokens, with no padding in between.  This
-        needs the decode_attn_split kernel (per-sequence positions)."""
+        needs the decode_attn_split kernel (per-sequence positions).
+
+        With lookahead > 1 a replay emits 1..lookahead tokens per sequence
+        and the call replays until every sequence has its n tokens
+        (last_replays says how often); the result is the same.  hint_ids
+        [b, n_hint] (n_hint <= max_len) is a guess of the continuation, a
+        previous answer or the text being edited: it only seeds the draft
+        lookup and cannot change the result."""
         n = min(max_new_tokens or self.max_new, self.max_new)
+        if hint_ids is not None and self.lookahead == 1:
+            raise ValueError("hint_ids needs lookahead > 1")
+        if self.lookahead > 1:
+            return self._generate_lookahead(prompt_ids, n, eos_token_id,
+                                            prompt_lens, hint_ids)
         if prompt_lens is not None:
             prompt_lens = torch.as_tensor(prompt_lens)
         if prompt_lens is not None and not (self._fused_attn
@@ -444,6 +549,63 @@ class GraphedDecoder:
         self.step_i.add_(1)
         for _ in range(n - 1):
             self._graph.replay()
+        self.last_replays = n - 1
+        return self._result(prompt_ids, n, eos_token_id, prompt_lens)
+
+    def _generate_lookahead(self, prompt_ids, n, eos_token_id, prompt_lens,
+                            hint_ids):
+        if prompt_lens is not None:
+            prompt_lens = torch.as_tensor(prompt_lens)
+        self._start_lookahead(prompt_ids, prompt_lens, hint_ids)
+        self._run_lookahead(n)
+        return self._result(prompt_ids, n, eos_token_id, prompt_lens)
+
+    def _start_lookahead(self, prompt_ids, prompt_lens=None, hint_ids=None):
+        """Capture if needed, prefill, seed the corpus and the first drafts;
+        leaves one emitted token per sequence (the prefill's)."""
+        T, plen = self.lookahead, prompt_ids.shape[1]
+        assert plen + self.max_new + T <= self.max_len, "window too small"
+        if hint_ids is not None:
+            assert hint_ids.dim() == 2 and \
+                hint_ids.shape[0] == self.batch and \
+                hint_ids.shape[1] <= self.max_len, "hint_ids not [b, <= max_len]"
+        if self._graph is None:
+            # scratch state for the 2 warm-up steps and the capture: each
+            # advances pos by at most T
+            self.pos.fill_(max(0, min(plen, self.max_len - 4 * T)))
+            self.count.zero_()
+            self.hint_n.zero_()
+            self._capture()
+        self._prefill(prompt_ids, prompt_lens)  # tok = the first new token
+        nh = 0 if hint_ids is None else hint_ids.shape[1]
+        self.hint_n.fill_(nh)
+        self.corpus.zero_()
+        if nh:
+            self.corpus[:, :nh] = hint_ids.to(self.dev)
+        self.corpus[:, nh:nh + plen] = prompt_ids.to(self.dev)
+        self.corpus.scatter_(1, (self.hint_n + self.pos)[:, None],
+                             self.tok[:, :1])
+        self.out_tokens[:, :1] = self.tok[:, :1]
+        self.count.fill_(1)
+        self._draft()
+
+    def _run_lookahead(self, n):
+        """Replay until every sequence has n tokens.  A replay emits at most
+        T tokens per sequence, so the slowest sequence needs at least
+        ceil(missing / T) more: that many are replayed between two host
+        reads of the counts.  No replay is wasted, and the reads are few
+        when drafts are accepted."""
+        T = self.lookahead
+        self.last_replays = 0
+        while True:
+            missing = n - int(self.count.min())
+            if missing <= 0:
+                break
+            for _ in range((missing + T - 1) // T):
+                self._graph.replay()
+                self.last_replays += 1
+
+    def _result(self, prompt_ids, n, eos_token_id, prompt_lens):
         toks = self.out_tokens[:, :n].clone()
         if eos_token_id is not None:
             # trim after the first EOS per row (host-side, post hoc)
